@@ -28,8 +28,23 @@ algorithm), and the segment tree's gain is reported as speedup_vs_bruteforce
 against the device's own brute-force scan kernel (never as a roofline
 fraction).
 
+A plain run does what the headline figure needs: it sets up, runs --warmup steps, times
+--steps steps and prints the line (metric, value, ms_per_step, and what the timed steps'
+own timers give: roofline, host_breakdown, cold.first_handle). --full adds the legs that
+take runs of their own: the CPU baseline, the apparent-resistivity report and its
+comparisons with the reference, a fresh handle's first solve (cold) and, for
+wenner_topography, the brute-force scan kernel and the physical survey; --no-cpu,
+--no-rho and --no-bruteforce drop single legs of a --full run.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as
+DIR/<name>.npy (rank 0): u [E, 1] float32 and point_sums [E, 3] float64 (sum, sum^2,
+steps per point), or, for wenner_topography, the survey's rho_a, rho_a_se and the model
+and background dV and their errors [Q] float64. The seeds are fixed, so two runs with
+the same arguments solve the same walks.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
                        [--workload dcr_dipole|wenner_topography|variable_coefficients]
+                       [--full] [--dump-outputs DIR]
        --gpus N > 1 starts N rank processes itself (launch_ranks; the parent makes no HIP
        call); under a launcher (python -m torch.distributed.run --nproc-per-node N
        bench.py --gpus N ...) WORLD_SIZE must equal --gpus.
@@ -63,7 +78,14 @@ def parse():
                     help="wenner_topography: the notebook's conductivity with its air term (literal, SURVEY 8d "
                          "C5; the timed survey) or without it (physical); the rho_a report always comes from "
                          "a physical survey")
-    ap.add_argument("--no-bruteforce", action="store_true", help="wenner_topography: skip the scan-kernel leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the headline figure: CPU baseline, apparent resistivity and "
+                         "its comparisons with the reference, a fresh handle's cold start, and for "
+                         "wenner_topography the brute-force scan kernel and the physical survey")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-bruteforce", action="store_true",
+                    help="with --full, wenner_topography: skip the scan-kernel leg")
     ap.add_argument("--handle-pairs", type=int, default=None,
                     help="wenner_topography: (model, background) solver pairs, one host thread and HIP stream each "
                          "(1 / 2 / 3 pairs: 1.357 / 1.377 / 1.409e10 walk-steps/s, profiles/r04_ab/c5_handle_pairs_ab.log). "
@@ -76,12 +98,26 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-baseline sample")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: N x --walks walks per electrode on N GPUs (default); strong: --walks on N GPUs")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-rho", action="store_true", help="skip the apparent-resistivity leg (profiling runs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-rho", action="store_true",
+                    help="with --full: skip the apparent-resistivity leg (profiling runs)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="only launch the ranks: each prints its RANK/LOCAL_RANK/WORLD_SIZE as JSON (no GPU)")
     ap.add_argument("--dry-launch-fail-rank", type=int, default=None, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:   # a plain run: the timed steps alone
+        args.no_cpu = args.no_rho = args.no_bruteforce = True
+    return args
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <path>/<name>.npy, float32 or float64 as computed."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 CPU_SEED = 321
@@ -492,12 +528,14 @@ def main():
         if comm is not None:
             comm.barrier()
 
+    last_u = {}   # id(solver) -> the u [E, 1] its last solve returned
+
     def one_step(seed, slv=solver):
         """One survey solve; the per-electrode (sum, sum^2, steps) end up in slv.last_point_sums."""
         if comm is None:
-            slv.solve(sc.points, nWalks=Wt, maxSteps=sc.max_steps, eps=sc.eps, seed=seed)
+            last_u[id(slv)] = slv.solve(sc.points, nWalks=Wt, maxSteps=sc.max_steps, eps=sc.eps, seed=seed)
         else:
-            C.solve_distributed(slv, comm, sc.points, Wt, sc.max_steps, sc.eps, seed=seed)
+            last_u[id(slv)] = C.solve_distributed(slv, comm, sc.points, Wt, sc.max_steps, sc.eps, seed=seed)[0]
         return slv.last_timing
 
     cold = {}
@@ -555,6 +593,8 @@ def main():
         per_rank = rank_breakdown(comm, {"elapsed_ms": 1e3 * elapsed, "kernel_ms": kernel_ms, **phase,
                                          "walk_steps": steps_local})
     last_sums = solver.last_point_sums
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, {"u": last_u[id(solver)], "point_sums": last_sums})
 
     # apparent resistivity (second half of the metric), outside the timed region: the
     # homogeneous-background survey on the same walk streams as the last timed step
@@ -647,7 +687,7 @@ def main():
             med["tail_share_of_kernel"] = med["tail_ms"] / med["walk_kernel_ms"]
         out["host_breakdown"] = med
         out["libwost"] = libinfo
-        if comm is None:
+        if comm is None and args.full:
             def fresh_solve(slv):
                 slv.solve(sc.points, nWalks=Wt, maxSteps=sc.max_steps, eps=sc.eps, seed=7)
                 return slv.last_timing
@@ -779,6 +819,11 @@ def wenner_main(args, world, rank, local):
         # (kernel_ms sums both fields' concurrent kernels: it can exceed elapsed_ms)
         per_rank = rank_breakdown(comm, {"elapsed_ms": 1e3 * elapsed, "kernel_ms": kernel_ms, **phase,
                                          "walk_steps": steps_local})
+    if args.dump_outputs and rank == 0 and res is not None:
+        dump_outputs(args.dump_outputs, {"rho_a": res.rho.rho_a, "rho_a_se": res.rho.se,
+                                         "dv_model": res.model.dv, "dv_model_se": res.model.se,
+                                         "dv_background": res.background.dv,
+                                         "dv_background_se": res.background.se})
     res_phys = None
     pm = ph = None
     if args.fields == "literal" and not args.no_rho:   # outside the timed region: the physical survey's rho_a

@@ -9,7 +9,7 @@ TR="python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 
 bash tools/gpu_session.sh \
   "gputests|700|python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread" \
   "smoke|300|python -c 'import __graft_entry__ as g; g.smoke()'" \
-  "bench|400|python bench.py" \
-  "bench_c5|400|python bench.py --workload wenner_topography --steps 5 --warmup 1" \
-  "bench_comm|300|WOST_BENCH_FORCE_COMM=1 $TR bench.py --steps 5 --warmup 1 --no-cpu" \
-  "bench_c5_comm|300|WOST_BENCH_FORCE_COMM=1 $TR bench.py --workload wenner_topography --steps 3 --warmup 1 --no-cpu --no-bruteforce"
+  "bench|400|python bench.py --full" \
+  "bench_c5|400|python bench.py --full --workload wenner_topography --steps 5 --warmup 1" \
+  "bench_comm|300|WOST_BENCH_FORCE_COMM=1 $TR bench.py --full --steps 5 --warmup 1 --no-cpu" \
+  "bench_c5_comm|300|WOST_BENCH_FORCE_COMM=1 $TR bench.py --full --workload wenner_topography --steps 3 --warmup 1 --no-cpu --no-bruteforce"

@@ -11,7 +11,7 @@ B="$R/bench.py"
 S="$R/tools/gpu_session.sh"
 PMC_ARGS="--steps 2 --warmup 1 --no-cpu --no-rho"
 "$S" \
-  "bench|300|python3 $B" \
+  "bench|300|python3 $B --full" \
   "stats|300|rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $B --steps 4 --warmup 1 --no-cpu --no-rho" \
   "pmc_fetch|300|rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python3 $B $PMC_ARGS" \
   "pmc_write|300|rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run -- python3 $B $PMC_ARGS" \
