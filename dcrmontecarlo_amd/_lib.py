@@ -122,6 +122,8 @@ def _load():
                                        POINTER(c_uint32)]),
         "wost_last_timing": (c_int32, [H, POINTER(WostTiming)]),
         "wost_num_sources": (c_int32, [H, POINTER(c_int32)]),
+        "wost_set_wavenumbers": (c_int32, [H, POINTER(c_double), c_int32]),
+        "wost_num_channels": (c_int32, [H, POINTER(c_int32)]),
         "wost_solve_range": (c_int32, [H, POINTER(c_float), c_int64, c_int64, c_int64, c_int64, c_int32, c_float,
                                        c_uint64, POINTER(c_double), POINTER(c_double), POINTER(c_float),
                                        POINTER(c_uint32)]),
@@ -158,6 +160,8 @@ def _load():
         "wost_kernel_source": (c_int32, [POINTER(WostProblem), ctypes.c_char_p, c_int64, POINTER(c_int64)]),
         "wost_kernel_source_sources": (c_int32, [POINTER(WostProblem), POINTER(POINTER(WostField)), c_int32,
                                                  ctypes.c_char_p, c_int64, POINTER(c_int64)]),
+        "wost_kernel_source_channels": (c_int32, [POINTER(WostProblem), POINTER(POINTER(WostField)), c_int32, c_int32,
+                                                  ctypes.c_char_p, c_int64, POINTER(c_int64)]),
         "wost_jit_compile": (c_int32, [ctypes.c_char_p, ctypes.c_char_p, c_int32, POINTER(c_uint8), c_int64,
                                        POINTER(c_int64), POINTER(c_int32)]),
         "wost_eval_field": (c_int32, [H, c_int32, POINTER(c_float), c_int64, POINTER(c_float)]),

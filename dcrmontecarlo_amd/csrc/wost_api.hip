@@ -186,6 +186,11 @@ struct wost_handle {
     std::vector<float> dverts, nverts;
     HostField fields[N_FIELDS];   // N_SLOTS problem fields, then sources 1.. of wost_set_sources
     int n_sources = 1;
+    // 2.5-D wavenumbers (wost_set_wavenumbers): k^2 per wavenumber, 0 = none set; a solve
+    // scores channels() = max(1, n_wavenumbers) * n_sources values per walk
+    int n_wavenumbers = 0;
+    float k2[WOST_MAX_SOURCES] = {};
+    int channels() const { return (n_wavenumbers > 0 ? n_wavenumbers : 1) * n_sources; }
     bool delta = false;
     double sigma_bar = 0.0;
     Program prog;
@@ -293,6 +298,7 @@ bool exact_trig_of(const wost_handle* h) {
 // options and trig choice, the launch's workgroup, staging and polyline placement.
 int jit_source(const wost_handle* h, const Program& prog, int mode, bool record, int ns, int block,
                bool global_polylines, int tree_stage, std::string* src) {
+    const int nk = mode_delta(mode) ? h->n_wavenumbers : 0;   // (0: none set, the kernel without the k2 read)
     const int nn = (int)(h->nverts.size() / 2);
     std::vector<float> phi;   // a compiled-in Neumann polyline carries the device's segment angles
     if (jit_const_neumann(h->opt, mode, nn) && nn >= 2) {
@@ -301,7 +307,7 @@ int jit_source(const wost_handle* h, const Program& prog, int mode, bool record,
     }
     *src = jit_generate(h->opt, mode, *prog.hdr(), prog.terms(), prog.factors(), h->dverts.data(),
                         (int)(h->dverts.size() / 2), h->nverts.data(), nn, record, ns, block,
-                        phi.empty() ? nullptr : phi.data(), global_polylines, tree_stage, exact_trig_of(h));
+                        phi.empty() ? nullptr : phi.data(), global_polylines, tree_stage, exact_trig_of(h), nk);
     return WOST_OK;
 }
 
@@ -310,8 +316,9 @@ int jit_source(const wost_handle* h, const Program& prog, int mode, bool record,
 // at most 1024) and the trig choice
 int jit_key(const wost_handle* h, int mode, bool record, int ns, int block, bool global_polylines, int tree_stage) {
     const bool exact = exact_trig_of(h);
-    return (((((2 * mode + (record ? 1 : 0)) * (WOST_MAX_SOURCES + 1) + ns) * 3 + tree_stage) * 17 + block / 64) * 2 +
-            (global_polylines ? 1 : 0)) * 2 + (exact ? 1 : 0);
+    const int nk = mode_delta(mode) ? h->n_wavenumbers : 0;
+    return ((((((2 * mode + (record ? 1 : 0)) * (WOST_MAX_SOURCES + 1) + ns) * (WOST_MAX_SOURCES + 1) + nk) * 3 +
+              tree_stage) * 17 + block / 64) * 2 + (global_polylines ? 1 : 0)) * 2 + (exact ? 1 : 0);
 }
 
 // jit_kernel without blocking on a compile (option jit_race): kReady with the handle's
@@ -969,9 +976,12 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
                double* point_stats, float* walk_values, uint32_t* walk_steps, float* records, bool multi = false,
                int64_t walk_begin = 0, int64_t walk_end = -1) {
     if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
-    const int ns = h->n_sources;
+    const int n_src = h->n_sources;
+    const int ns = h->channels();   // values per walk: channel c = j * n_src + s (wavenumber j, source s)
     if (ns != 1 && !multi)
-        return fail(WOST_ERR_INVALID_ARG, "the handle has %d sources (wost_set_sources): use wost_solve_multi", ns);
+        return fail(WOST_ERR_INVALID_ARG,
+                    "the handle scores %d channels (%d sources of wost_set_sources x %d wavenumbers of "
+                    "wost_set_wavenumbers): use wost_solve_multi", ns, n_src, ns / n_src);
     const int row = 2 * ns + 1;   // doubles per block / point row
     if (n_points < 0 || (n_points > 0 && !points)) return fail(WOST_ERR_INVALID_ARG, "bad points");
     if (W <= 0) return fail(WOST_ERR_INVALID_ARG, "nWalks must be >= 1 (got %lld)", (long long)W);
@@ -1112,7 +1122,7 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
     const Options& O = h->opt;
     double jit_ms = 0.0;
     auto stage_of = [](int recs, int verts) { return recs > 0 ? (verts > 0 ? 2 : 1) : 0; };
-    hipFunction_t jfn = jit_kernel(h, mode, records != nullptr, ns, block, gpoly, stage_of(tree_lds, tree_verts),
+    hipFunction_t jfn = jit_kernel(h, mode, records != nullptr, n_src, block, gpoly, stage_of(tree_lds, tree_verts),
                                    &jit_ms);
     if (!jfn && block != kWalkBlock) {   // the precompiled kernels run 256-thread workgroups, no staged tree
         block = kWalkBlock;
@@ -1120,7 +1130,7 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
         tree_verts = 0;
     }
     if (ns > 1 && !jfn)
-        return fail(WOST_ERR_UNSUPPORTED, "multi-source solves need the field-specialised kernel%s%s",
+        return fail(WOST_ERR_UNSUPPORTED, "multi-source and multi-wavenumber solves need the field-specialised kernel%s%s",
                     h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
     size_t lds = walk_lds_bytes(mode, nd_, nn_, (int)n_points, tree_lds, jfn && jit_const_dirichlet(O, nd_),
                                 jfn && jit_const_neumann(O, mode, nn_), jfn && gpoly, block, tree_verts);
@@ -1143,13 +1153,14 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
         // from 256-thread workgroups
         tree_level = tree_verts > 0 ? 1 : 0;
         tree_lds = tree_lds_records(h, mode, tree_level, &block, &tree_verts);
-        if (!(jfn = jit_kernel(h, mode, records != nullptr, ns, block, gpoly, stage_of(tree_lds, tree_verts),
+        if (!(jfn = jit_kernel(h, mode, records != nullptr, n_src, block, gpoly, stage_of(tree_lds, tree_verts),
                                &jit_ms))) {
             // the precompiled kernels then (256-thread workgroups, nothing of the tree staged)
             block = kWalkBlock;
             tree_lds = tree_verts = 0;
             if (ns > 1)
-                return fail(WOST_ERR_UNSUPPORTED, "multi-source solves need the field-specialised kernel: %s",
+                return fail(WOST_ERR_UNSUPPORTED,
+                            "multi-source and multi-wavenumber solves need the field-specialised kernel: %s",
                             h->jit_error.c_str());
             break;
         }
@@ -1185,6 +1196,7 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
     a.rec = d_rec;
     a.rec_stride = (int32_t)rec_stride;
     a.exact_trig = exact_trig_of(h) ? 1 : 0;
+    for (int j = 0; j < h->n_wavenumbers; ++j) a.k2[j] = h->k2[j];   // (the rest 0)
     if (mode_tree(mode)) {
         a.tree = reinterpret_cast<const float4*>(h->d_tree);
         a.tree_first_leaf = h->tree.first_leaf;
@@ -1198,7 +1210,8 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
         // walk pools (wost_walk.h): near = within pool_near (default 0.1) of the Neumann
         // polyline's largest extent from its bounding box; tree_pool = 0 turns them off,
         // pool_slots (default 128) walks per class and workgroup
-        if (O.tree_pool != 0 && h->nverts.size() >= 4) {
+        // (a parked walk holds one attenuation: launches of several wavenumbers run without pools)
+        if (O.tree_pool != 0 && h->nverts.size() >= 4 && h->n_wavenumbers <= 1) {
             float x0 = h->nverts[0], x1 = x0, y0 = h->nverts[1], y1 = y0;
             for (size_t i = 2; i + 1 < h->nverts.size(); i += 2) {
                 x0 = std::min(x0, h->nverts[i]); x1 = std::max(x1, h->nverts[i]);
@@ -1208,7 +1221,7 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
             const int slots = O.pool_slots;
             const float m = frac * std::max(x1 - x0, y1 - y0);
             // (study builds, tree_iter_stats: 16 counter words after each workgroup's pools)
-            const int64_t words = (int64_t)pool_wg_words(ns, slots) + (O.tree_iter_stats ? 16 : 0);
+            const int64_t words = (int64_t)pool_wg_words(n_src, slots) + (O.tree_iter_stats ? 16 : 0);
             if ((rc = ensure_cap(h->d_pool, h->pool_cap, words * (int64_t)blocks_per_cu * h->num_cus)) != WOST_OK)
                 return rc;
             a.pool = h->d_pool;
@@ -1628,7 +1641,7 @@ int wost_solve(wost_handle* h, const float* points, int64_t n_points, int64_t W,
                double* block_stats, double* point_stats, float* walk_values, uint32_t* walk_steps) {
     // a whole single-source solve may start on the precompiled kernel while its specialised
     // one compiles (solve_race)
-    if (h && h->jit_enabled && h->opt.jit_race && h->n_sources == 1 && n_points > 0 && W > 0 && block_begin == 0 &&
+    if (h && h->jit_enabled && h->opt.jit_race && h->channels() == 1 && n_points > 0 && W > 0 && block_begin == 0 &&
         block_end == wost_num_blocks(n_points, W) && max_steps >= 0 && eps == eps)
         return solve_race(h, points, n_points, W, max_steps, eps, seed, block_stats, point_stats, walk_values,
                           walk_steps);
@@ -1645,7 +1658,7 @@ int wost_solve_range(wost_handle* h, const float* points, int64_t n_points, int6
         return solve_impl(h, points, n_points, W, 0, nb, max_steps, eps, seed, block_stats, point_stats,
                           walk_values, walk_steps, nullptr, true);
     }
-    const int ns = h->n_sources;
+    const int ns = h->channels();
     const int64_t chunk = (kMaxBatchWalks / ns) / WOST_BLOCK_WALKS * WOST_BLOCK_WALKS;   // walks of a point per launch
     if (walk_end - walk_begin <= chunk || walk_begin < 0 || walk_end <= walk_begin || n_points <= 0)
         return solve_impl(h, points, n_points, W, 0, 0, max_steps, eps, seed, block_stats, point_stats, walk_values,
@@ -1710,6 +1723,9 @@ int wost_set_sources(wost_handle* h, const wost_field* const* sources, int32_t n
     std::vector<HostField> f(N_FIELDS);
     int rc = fields_with_sources(h, sources, n, f.data());
     if (rc != WOST_OK) return rc;
+    if (h->n_wavenumbers > 0 && n * h->n_wavenumbers > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "%d sources x %d wavenumbers exceed %d channels", n, h->n_wavenumbers,
+                    WOST_MAX_SOURCES);
     for (int s = 0; s < N_FIELDS; ++s) h->fields[s] = std::move(f[s]);
     h->n_sources = n;
     h->prog_dirty = true;
@@ -1723,6 +1739,9 @@ int wost_prepare_sources(wost_handle* h, const wost_field* const* sources, int32
     std::vector<HostField> f(N_FIELDS);
     int rc = fields_with_sources(h, sources, n, f.data());
     if (rc != WOST_OK) return rc;
+    if (h->n_wavenumbers > 0 && n * h->n_wavenumbers > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "%d sources x %d wavenumbers exceed %d channels", n, h->n_wavenumbers,
+                    WOST_MAX_SOURCES);
     if (!h->jit_enabled)
         return fail(WOST_ERR_UNSUPPORTED, "multi-source solves need the field-specialised kernel (disabled by wost_set_jit)");
     Program prog;
@@ -1744,14 +1763,21 @@ int wost_prepare_sources(wost_handle* h, const wost_field* const* sources, int32
     return WOST_OK;
 }
 
-int wost_kernel_source_sources(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
-                               char* out, int64_t capacity, int64_t* length) {
+int wost_kernel_source_channels(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
+                                int32_t n_wavenumbers, char* out, int64_t capacity, int64_t* length) {
     if (!pb || !length) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
     if (n_sources < 0 || n_sources > WOST_MAX_SOURCES || (n_sources > 0 && !sources))
         return fail(WOST_ERR_INVALID_ARG, "need 0..%d sources", WOST_MAX_SOURCES);
+    if (n_wavenumbers < 0 || n_wavenumbers * std::max(n_sources, 1) > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "need sources x wavenumbers <= %d channels", WOST_MAX_SOURCES);
     wost_handle* h = nullptr;
     int rc = create_host(pb, &h);
     if (rc != WOST_OK) return rc;
+    if (n_wavenumbers > 0 && !h->delta) {
+        delete h;
+        return fail(WOST_ERR_UNSUPPORTED, "wavenumbers need delta tracking: give sigma or alpha (a constant alpha is enough)");
+    }
+    h->n_wavenumbers = n_wavenumbers;
     int ns = 1;
     if (n_sources >= 1) {   // wost_set_sources' fields, without a device
         for (int k = 0; k < n_sources; ++k) {
@@ -1787,7 +1813,8 @@ int wost_kernel_source_sources(const wost_problem* pb, const wost_field* const* 
 #endif
     const std::string src = jit_generate(h->opt, mode, *h->prog.hdr(), h->prog.terms(), h->prog.factors(), h->dverts.data(),
                                          (int)(h->dverts.size() / 2), h->nverts.data(), nn, false, ns, block,
-                                         phi.empty() ? nullptr : phi.data(), false, stage, exact_trig_of(h));
+                                         phi.empty() ? nullptr : phi.data(), false, stage, exact_trig_of(h),
+                                         mode_delta(mode) ? n_wavenumbers : 0);
     delete h;
     *length = (int64_t)src.size();
     if (out && capacity > 0) {
@@ -1795,6 +1822,43 @@ int wost_kernel_source_sources(const wost_problem* pb, const wost_field* const* 
         std::memcpy(out, src.data(), n);
         out[n] = '\0';
     }
+    return WOST_OK;
+}
+
+int wost_kernel_source_sources(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
+                               char* out, int64_t capacity, int64_t* length) {
+    return wost_kernel_source_channels(pb, sources, n_sources, 0, out, capacity, length);
+}
+
+int wost_set_wavenumbers(wost_handle* h, const double* k2, int32_t n) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    if (n < 0 || (n > 0 && !k2)) return fail(WOST_ERR_INVALID_ARG, "need n >= 0 wavenumbers");
+    if (n == 0) {
+        h->n_wavenumbers = 0;
+        std::fill(h->k2, h->k2 + WOST_MAX_SOURCES, 0.0f);
+        return WOST_OK;
+    }
+    if (!h->delta)
+        return fail(WOST_ERR_UNSUPPORTED,
+                    "wavenumbers need delta tracking (the screening k^2 alpha enters through the collision weight): "
+                    "create the solver with sigma or alpha -- a constant alpha is enough");
+    if ((int64_t)n * h->n_sources > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "%d wavenumbers x %d sources exceed %d channels", n, h->n_sources,
+                    WOST_MAX_SOURCES);
+    float v[WOST_MAX_SOURCES] = {};
+    for (int j = 0; j < n; ++j) {
+        if (!(k2[j] >= 0.0) || !std::isfinite(k2[j]) || !std::isfinite((float)k2[j]))
+            return fail(WOST_ERR_INVALID_ARG, "k2[%d] = %g must be finite and >= 0", j, k2[j]);
+        v[j] = (float)k2[j];
+    }
+    std::copy(v, v + WOST_MAX_SOURCES, h->k2);
+    h->n_wavenumbers = n;
+    return WOST_OK;
+}
+
+int wost_num_channels(const wost_handle* h, int32_t* n_channels) {
+    if (!h || !n_channels) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
+    *n_channels = h->channels();
     return WOST_OK;
 }
 

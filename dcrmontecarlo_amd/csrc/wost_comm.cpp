@@ -407,7 +407,7 @@ int wost_solve_distributed(wost_handle* h, wost_comm* c, const float* points, in
     // (wost_distributed_run), so that no rank is left waiting in the gather
     int32_t ns = 1;
     int32_t row = 3;
-    if (!h || wost_num_sources(h, &ns) != WOST_OK) row = 0;
+    if (!h || wost_num_channels(h, &ns) != WOST_OK) row = 0;
     else row = 2 * ns + 1;
     if (n_points > 0 && !points) row = 0;
     RcclRun run{h, c, points, n_points, walks_per_point, max_steps, eps, seed};

@@ -707,7 +707,7 @@ bool jit_fused_neumann_scan(const Options& o, int mode, int nn) {
 std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, const DTerm* terms, const DFactor* factors,
                          const float* dverts, int nd, const float* nverts, int nn, bool record, int n_sources,
                          int block, const float* seg_phi, bool global_polylines, int tree_stage,
-                         bool exact_trig) {
+                         bool exact_trig, int n_wavenumbers) {
     const bool neu = mode_neu(mode);
     const bool src = mode_src(mode);
     const bool delta = mode_delta(mode);
@@ -731,6 +731,8 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
     if (xf & 131072) o << "#define WOST_EXP_SCAN_BITS 1\n";   // A/B: neumann_scan_both's per-vertex bits
     if ((xf >> 18) & 1023) o << "#define WOST_ABL_DUP " << ((xf >> 18) & 1023) << "\n";   // phase_dup.sh
     o << "#define WOST_JIT_TRIG_EXACT " << (exact_trig ? 1 : 0) << "\n";   // wost_set_trig
+    // wavenumbers set (wost_set_wavenumbers): the collision weight reads WalkArgs::k2
+    if (n_wavenumbers >= 1) o << "#define WOST_WAVENUMBERS 1\n";
     if (xf & 2048) o << "#define WOST_EXP_IEEE_SQRT 1\n";
     // the handle's bit-preserving kernel options (wost_set_option; -1: the kernel's default)
     if (opt.philox_ahead >= 0) o << "#define WOST_PHILOX_AHEAD " << opt.philox_ahead << "\n";
@@ -900,7 +902,9 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
       << "    wost::walk_body<" << (neu ? "true" : "false") << ", " << (src ? "true" : "false") << ", "
       << (delta ? "true" : "false") << ", " << (tree ? "true" : "false") << ", " << (record ? "true" : "false")
       << ", " << n_sources << ", " << (mode_fix(mode) ? "true" : "false") << ", "
-      << (global_polylines ? "true" : "false") << ">(A, fld, smem);\n}\n";
+      << (global_polylines ? "true" : "false");
+    if (n_wavenumbers >= 1) o << ", " << n_wavenumbers;   // NK (a handle without wavenumbers: its kernel as ever)
+    o << ">(A, fld, smem);\n}\n";
     if (delta)   // alpha at the query points, with these fields (WalkArgs::point_alpha)
         o << "extern \"C\" __global__ void __launch_bounds__(256)\n"
           << "wost_point_alpha_jit(const char* prog, const float2* pts, long long n, float* out) {\n"

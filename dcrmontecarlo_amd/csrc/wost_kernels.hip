@@ -7,6 +7,8 @@
 // Per-walk results go to HBM; wost_block_reduce then sums them per block of
 // WOST_BLOCK_WALKS walks in a fixed order (deterministic, GPU-count
 // independent).
+// the interpreting kernels honour WalkArgs::k2[0] (a single wavenumber; wost_walk.h)
+#define WOST_WAVENUMBERS 1
 #include "wost_device.h"
 #include "wost_internal.h"
 

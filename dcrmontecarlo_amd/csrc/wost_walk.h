@@ -97,6 +97,11 @@ struct WalkArgs {
     // is thus a function of this call alone, never of an earlier one.
     uint32_t chunk_share;
     uint32_t waves;
+    // 2.5-D wavenumbers (wost_set_wavenumbers; delta tracking): channel j of a walk weights a
+    // collision by 1 - (sigma' + k2[j]) / sigma_bar. Read at run time (wave-uniform scalar
+    // loads), so one kernel per (problem, NS, NK) serves every wavenumber set; all 0 when none
+    // is set, and only kernels built with WOST_WAVENUMBERS read it.
+    float k2[WOST_MAX_SOURCES];
 };
 
 // The walk launch's control words (WalkArgs::counter): [0] the work-queue head, [1] the
@@ -736,6 +741,19 @@ __device__ __forceinline__ Hit intersect_polylines_tree_wave(const SegTree& t, f
 // GL: the polylines (and segment angles) are read from global memory instead of being
 // staged in LDS -- field-specialised kernels for polylines too long for the LDS budget
 // (wost_api.hip kGlobalPolylineLdsBytes).
+// NK > 1 (2.5-D wavenumber batching): under delta tracking a walk's path depends
+// only on sigma_bar -- the step, the collision test and the sampler never read sigma' --
+// and sigma' enters through the collision weight alone. The screened problem of wavenumber
+// k has sigma'_k = sigma' + k^2 (A.k2[j]), so one walk carries NK attenuations w[j] and
+// scores NK * NS channels, channel c = j * NS + s (wavenumber major): per-walk values go to
+// out_val[local walk * NK * NS + c], and every channel's total is bit for bit that of a
+// single solve of (k2[j], source s). Kernels built with WOST_WAVENUMBERS 1 read A.k2 (the
+// precompiled ones, NK = 1, and the specialised ones of a handle with wavenumbers set); the
+// others compile the add out, so a handle without wavenumbers runs the kernel it always ran.
+// NK > 1 tree kernels run without walk pools (a parked walk holds one w).
+#ifndef WOST_WAVENUMBERS
+#define WOST_WAVENUMBERS 0
+#endif
 // Walk pools (TREE kernels): see the exchange in walk_body. WOST_TREE_POOL 0 compiles
 // them out; WOST_POOL_MIN_PUSH: fewest mismatched walks a wave parks at once.
 #ifndef WOST_TREE_POOL
@@ -844,12 +862,15 @@ __device__ __forceinline__ void walk_sincos(float theta, float& sn, float& cs, b
 #define WOST_PIN_U4(u) ((void)0)
 #endif
 template <bool NEU, bool SRC, bool DELTA, bool TREE, bool REC, int NS = 1, bool FIX = false, bool GL = false,
-          class F>
+          int NK = 1, class F>
 __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsigned char* smem) {
     // the walk's position updates round op by op like the reference (torch CPU
     // has no FMA contraction); the field math it calls keeps its own setting
 #pragma clang fp contract(off)
     static_assert(NS >= 1 && (NS == 1 || SRC) && (NS == 1 || !REC), "multi-source walks need a source, no recorder");
+    static_assert(NK >= 1 && (NK == 1 || (DELTA && !REC && WOST_WAVENUMBERS)) && NK * NS <= WOST_MAX_SOURCES,
+                  "wavenumber channels need delta tracking, no recorder, at most WOST_MAX_SOURCES channels");
+    constexpr int NC = NK * NS;   // channels: c = j * NS + s
     constexpr bool kStageD = !F::kConstDirichlet && !GL;
     // the Neumann polyline is staged also when compiled in (FIX scans sN itself; a few
     // hundred bytes otherwise)
@@ -899,7 +920,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         for (int i = threadIdx.x; i < kGnormCells; i += blockDim.x) sG[i] = g[i];
     }
     // this workgroup's walk pools (header: lock, walks parked near, walks parked far)
-    uint32_t* const pool = (TREE && WOST_TREE_POOL && A.pool != nullptr)
+    uint32_t* const pool = (TREE && WOST_TREE_POOL && NK == 1 && A.pool != nullptr)
                                ? A.pool + (size_t)blockIdx.x * (size_t)A.pool_wg_words : nullptr;
     if (pool != nullptr && threadIdx.x < 4) pool[threadIdx.x] = 0u;
     __syncthreads();
@@ -947,12 +968,14 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     int k = 0;                  // step_count
     bool onB = false;           // onBoundary
     float phi = 0.f;            // atan2 of currentNormal (:228), set when onB
-    float w = 1.f;              // attenuation_coef
+    float w[NK];                // attenuation_coef (one per wavenumber)
+#pragma unroll
+    for (int j = 0; j < NK; ++j) w[j] = 1.f;
     float ax = 1.f;             // alpha(current_point), cached
     U4 rn_ahead{0u, 0u, 0u, 0u};   // (WOST_PHILOX_AHEAD) the words of this walk's step k
-    float total[NS];            // this walk's contributions (one per source)
+    float total[NC];            // this walk's contributions (one per channel)
 #pragma unroll
-    for (int s = 0; s < NS; ++s) total[s] = 0.f;
+    for (int c = 0; c < NC; ++c) total[c] = 0.f;
 #if defined(WOST_TREE_ITER_STATS)   // study build: the tree queries' loop counters (WOST_IC)
     uint32_t ic_arr[16];
 #pragma unroll
@@ -974,17 +997,22 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         if (kBatchEnd) batch = __popcll(__ballot(done || !active)) >= WOST_REFILL_MIN || !__any(active && !done);
         // --- walk termination: while-condition of :206, boundary term :295-298
         if (batch && done) {
-            float g = fld.has_g() ? fld.g(px, py) : 0.0f;
-            if (DELTA) g = g * w;
+            const float g0 = fld.has_g() ? fld.g(px, py) : 0.0f;
+            float g = g0;
+            if (DELTA) g = g0 * w[0];
 #pragma unroll
-            for (int s = 0; s < NS; ++s) total[s] = total[s] + g;
+            for (int j = 0; j < NK; ++j) {
+                const float gj = (DELTA && j > 0) ? g0 * w[j] : g;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) total[j * NS + s] = total[j * NS + s] + gj;
+            }
             const int64_t li = (int64_t)lid;
             if (REC && A.rec != nullptr) {
                 float* rr = A.rec + ((size_t)li * (size_t)A.rec_stride + (size_t)k) * kRecFloats;
                 rr[REC_X] = px; rr[REC_Y] = py; rr[REC_C] = g; rr[REC_AUX] = total[0];   // end record
             }
 #pragma unroll
-            for (int s = 0; s < NS; ++s) A.out_val[li * NS + s] = total[s];
+            for (int c = 0; c < NC; ++c) A.out_val[li * NC + c] = total[c];
             A.out_steps[li] = (uint32_t)k;
             if (kWaveStats) my_kmax = (uint32_t)k > my_kmax ? (uint32_t)k : my_kmax;
             active = false;
@@ -1025,7 +1053,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     r[4 * P] = __builtin_bit_cast(uint32_t, px); r[5 * P] = __builtin_bit_cast(uint32_t, py);
                     r[6 * P] = __builtin_bit_cast(uint32_t, dD);
                     r[7 * P] = (uint32_t)k | (onB ? 0x80000000u : 0u);
-                    r[8 * P] = __builtin_bit_cast(uint32_t, phi); r[9 * P] = __builtin_bit_cast(uint32_t, w);
+                    r[8 * P] = __builtin_bit_cast(uint32_t, phi); r[9 * P] = __builtin_bit_cast(uint32_t, w[0]);
                     r[10 * P] = __builtin_bit_cast(uint32_t, ax);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) r[(11 + s) * P] = __builtin_bit_cast(uint32_t, total[s]);
@@ -1045,7 +1073,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     dD = __builtin_bit_cast(float, r[6 * P]);
                     const uint32_t kb = r[7 * P];
                     k = (int)(kb & 0x7fffffffu); onB = (kb >> 31) != 0u;
-                    phi = __builtin_bit_cast(float, r[8 * P]); w = __builtin_bit_cast(float, r[9 * P]);
+                    phi = __builtin_bit_cast(float, r[8 * P]); w[0] = __builtin_bit_cast(float, r[9 * P]);
                     ax = __builtin_bit_cast(float, r[10 * P]);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) total[s] = __builtin_bit_cast(float, r[(11 + s) * P]);
@@ -1135,9 +1163,11 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 if (WOST_PHILOX_AHEAD) rn_ahead = philox_draw(pw, 0u, A.key0, A.key1);
                 const float2 q = A.points[pid];
                 px = q.x; py = q.y;
-                k = 0; dD = FIX ? WOST_INF : 1.0f; onB = false; phi = 0.f; w = 1.f;
+                k = 0; dD = FIX ? WOST_INF : 1.0f; onB = false; phi = 0.f;
 #pragma unroll
-                for (int s = 0; s < NS; ++s) total[s] = 0.f;
+                for (int j = 0; j < NK; ++j) w[j] = 1.f;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) total[c] = 0.f;
                 if (DELTA) ax = A.point_alpha[pid];                // alpha(x0), precomputed per point
                 active = true;
             }
@@ -1170,7 +1200,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     dD = __builtin_bit_cast(float, r[6 * P]);
                     const uint32_t kb = r[7 * P];
                     k = (int)(kb & 0x7fffffffu); onB = (kb >> 31) != 0u;
-                    phi = __builtin_bit_cast(float, r[8 * P]); w = __builtin_bit_cast(float, r[9 * P]);
+                    phi = __builtin_bit_cast(float, r[8 * P]); w[0] = __builtin_bit_cast(float, r[9 * P]);
                     ax = __builtin_bit_cast(float, r[10 * P]);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) total[s] = __builtin_bit_cast(float, r[(11 + s) * P]);
@@ -1385,31 +1415,36 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 }
             }
             WOST_PHASE("source_contribution");
-            if constexpr (NS == 1) {
+            if constexpr (NC == 1) {
                 float c = 0.0f;
                 if (!clipped) {
                     float f = fld.f(yx, yy);
                     if (WOST_ABL_DUP & 256) f = dup_merge(f, fld.f(dup_opq(yx), yy));
                     if (DELTA)
-                        c = (f * gnorm) * f_rsq(aj.v * ax) * w;  // :253-254
+                        c = (f * gnorm) * f_rsq(aj.v * ax) * w[0];  // :253-254
                     else
                         c = f * ((r * r) / 4.0f);                        // :256, utils.py:61
                 }
                 total[0] = total[0] + c;                                 // :258
                 cv = c;
-            } else if (!clipped) {                                       // the same per source
+            } else if (!clipped) {                                       // the same per channel
                 float fv[NS];
-                fld.f_multi(yx, yy, fv);
+                if constexpr (NS == 1) fv[0] = fld.f(yx, yy);
+                else fld.f_multi(yx, yy, fv);
                 const float sa = DELTA ? f_rsq(aj.v * ax) : 0.0f;
                 const float q = DELTA ? 0.0f : ((r * r) / 4.0f);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
-                    const float c = DELTA ? ((fv[s] * gnorm) * sa * w) : fv[s] * q;
-                    total[s] = total[s] + c;
+                    const float fg = DELTA ? ((fv[s] * gnorm) * sa) : fv[s] * q;
+#pragma unroll
+                    for (int j = 0; j < NK; ++j) {
+                        const float c = DELTA ? fg * w[j] : fg;
+                        total[j * NS + s] = total[j * NS + s] + c;
+                    }
                 }
             } else {
 #pragma unroll
-                for (int s = 0; s < NS; ++s) total[s] = total[s] + 0.0f;
+                for (int c = 0; c < NC; ++c) total[c] = total[c] + 0.0f;
             }
         }
         if (REC && A.rec != nullptr) {                               // :218-222, :261-266
@@ -1428,10 +1463,23 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             const bool collide = !(mu > sigma_bar * gnorm) && !clipped;
             float anew = aj.v;                                       // a collision, or a clipped sample (y = z)
             if (!collide && !clipped) anew = fld.alpha(xnx, xny);
-            float sc = 1.0f;
-            if (collide) sc = 1.0f - sigma_prime_from(aj, fld.sigma(yx, yy), fld.detached()) * inv_sb;
-            const float wt = w * f_sqrt(f_div(anew, ax));
-            w = collide ? wt * sc : wt;
+            float sc[NK];
+#pragma unroll
+            for (int j = 0; j < NK; ++j) sc[j] = 1.0f;
+            if (collide) {
+                const float spv = sigma_prime_from(aj, fld.sigma(yx, yy), fld.detached());
+#pragma unroll
+                for (int j = 0; j < NK; ++j) {
+                    if constexpr (WOST_WAVENUMBERS) sc[j] = 1.0f - (spv + A.k2[j]) * inv_sb;   // kept signed
+                    else sc[j] = 1.0f - spv * inv_sb;
+                }
+            }
+            const float wr = f_sqrt(f_div(anew, ax));                // shared by the wavenumbers
+#pragma unroll
+            for (int j = 0; j < NK; ++j) {
+                const float wt = w[j] * wr;
+                w[j] = collide ? wt * sc[j] : wt;
+            }
             px = collide ? yx : xnx;
             py = collide ? yy : xny;
             onB = collide ? false : onB;                             // a collision point is interior
@@ -1448,7 +1496,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 if (WOST_ABL_DUP & 128) anew = dup_merge(anew, fld.alpha(dup_opq(xnx), xny));
             }
 #endif
-            float sc = 1.0f;
+            float sc[NK];
+#pragma unroll
+            for (int j = 0; j < NK; ++j) sc[j] = 1.0f;
 #if defined(WOST_ABL_NO_SIGMA_PRIME)
             if (false) {
 #else
@@ -1458,11 +1508,20 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 if (WOST_ABL_DUP & 512)
                     spv = dup_merge(spv, sigma_prime_from(Jet{dup_opq(aj.v), aj.gx, aj.gy, aj.lap},
                                                           fld.sigma(dup_opq(yx), yy), fld.detached()));
-                sc = 1.0f - spv * inv_sb;
-                sc = (0.0f > sc) ? 0.0f : sc;                        // Python max(., 0.0) (:282)
+#pragma unroll
+                for (int j = 0; j < NK; ++j) {
+                    float scj;
+                    if constexpr (WOST_WAVENUMBERS) scj = 1.0f - (spv + A.k2[j]) * inv_sb;
+                    else scj = 1.0f - spv * inv_sb;
+                    sc[j] = (0.0f > scj) ? 0.0f : scj;               // Python max(., 0.0) (:282)
+                }
             }
-            const float wt = w * f_sqrt(f_div(anew, ax));           // :277 / :283
-            w = accept ? wt : wt * sc;
+            const float wr = f_sqrt(f_div(anew, ax));               // :277 / :283, shared by the wavenumbers
+#pragma unroll
+            for (int j = 0; j < NK; ++j) {
+                const float wt = w[j] * wr;
+                w[j] = accept ? wt : wt * sc[j];
+            }
             px = accept ? xnx : yx;
             py = accept ? xny : yy;
             ax = anew;

@@ -38,6 +38,9 @@ def _is_torch(a) -> bool:
 
 
 _TIMING_FIELDS = tuple(k for k, _ in _lib.WostTiming._fields_)
+# ... of these, the ones a solve of several launches adds up (solve_wavenumbers' chunks)
+_SUMMED_TIMINGS = ("walk_kernel_ms", "reduce_kernel_ms", "total_ms", "n_launches", "total_steps", "total_walks",
+                   "jit_ms", "span_ms", "precompiled_walks")
 
 
 def _points_np(a) -> np.ndarray:
@@ -106,10 +109,11 @@ def _problem(dxy, nxy, g, f, sigma, alpha, compat, device, sigma_bar):
 
 def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoundary=None, source=None,
                   sigma=None, alpha=None, *, sigma_bar: float | None = None, compat: str = "reference",
-                  sources=None) -> str:
+                  sources=None, n_wavenumbers: int = 0) -> str:
     """HIP source of the field-specialised walk kernel a WostSolver_2D with these
     arguments would compile (no device needed; wost_kernel_source). sources: the fields
-    of a multi-source solve (solve_sources; wost_kernel_source_sources)."""
+    of a multi-source solve (solve_sources; wost_kernel_source_sources); n_wavenumbers: the
+    wavenumbers of set_wavenumbers (wost_kernel_source_channels; 0: none)."""
     dxy = np.asarray(_np(dirichletBoundary.points), dtype=np.float32).reshape(-1, 2)
     nxy = None if neumannBoundary is None else np.asarray(_np(neumannBoundary.points), dtype=np.float32).reshape(-1, 2)
     conv = _Converter(_bounds_of(dxy, nxy))
@@ -125,8 +129,8 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
     packed = [_lib.make_field(conv(x, "source")) for x in (sources or [])]
     arr = (ctypes.POINTER(_lib.WostField) * max(1, len(packed)))(*[ctypes.pointer(wf) for wf, _ in packed])
     n = ctypes.c_int64(0)
-    call = lambda buf, cap: _lib.lib.wost_kernel_source_sources(ctypes.byref(prob), arr, len(packed), buf, cap,
-                                                                 ctypes.byref(n))
+    call = lambda buf, cap: _lib.lib.wost_kernel_source_channels(ctypes.byref(prob), arr, len(packed),
+                                                                  int(n_wavenumbers), buf, cap, ctypes.byref(n))
     _lib.check(call(None, 0), "wost_kernel_source")
     buf = ctypes.create_string_buffer(n.value + 1)
     _lib.check(call(buf, n.value + 1), "wost_kernel_source")
@@ -206,6 +210,7 @@ class WostSolver_2D:
         self.sigma_bar = float(sb.value) if self.use_delta_tracking else None
         self.last_timing = None
         self.last_point_sums = None   # (sum, sum^2, steps) per point of the last solve
+        self.wavenumbers = None       # set_wavenumbers: the k of the handle's channels, or None
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -271,13 +276,14 @@ class WostSolver_2D:
     def solve_range(self, solvePoints, nWalks: int, walk_begin: int, walk_end: int, maxSteps: int = 1000,
                     eps: float = 1e-4, seed: int = 0):
         """Walks [walk_begin, walk_end) of every point (block-aligned ends; wost_solve_range):
-        the (sum, sum^2, steps) rows of its blocks, [N, blocks, 3], each equal to the
+        the (sum, sum^2, steps) rows of its blocks, [N, blocks, 3] ([N, blocks, 2C+1] with C
+        channels: sources x wavenumbers), each equal to the
         corresponding block of the full solve. The unit of dcrmontecarlo_amd.comm's sharding."""
         p = _points_np(solvePoints)
         n = p.shape[0]
         nbr = -(-(int(walk_end) - int(walk_begin)) // _lib.WOST_BLOCK_WALKS)
-        ns = ctypes.c_int32(1)
-        _lib.check(_lib.lib.wost_num_sources(self._h, ctypes.byref(ns)), "wost_num_sources")
+        ns = ctypes.c_int32(1)   # values per walk: sources x wavenumbers
+        _lib.check(_lib.lib.wost_num_channels(self._h, ctypes.byref(ns)), "wost_num_channels")
         bs = np.zeros((n, max(nbr, 0), 2 * ns.value + 1), np.float64)
         _lib.check(_lib.lib.wost_solve_range(self._h, _lib.fptr(p), n, int(nWalks), int(walk_begin), int(walk_end),
                                              int(maxSteps), float(eps), int(seed) & (2**64 - 1), _lib.dptr(bs), None,
@@ -456,6 +462,11 @@ class WostSolver_2D:
         sums, vals, steps = [], [], None
         for c0 in range(0, len(fields), _lib.WOST_MAX_SOURCES):
             with self.sources_installed(fields[c0:c0 + _lib.WOST_MAX_SOURCES]) as S:
+                if self.num_channels() != S:   # (wost_solve_multi would write rows of 2C+1, values [walks][C])
+                    raise ValueError(f"solve_sources scores one value per source, but the solver has "
+                                     f"{self.num_channels() // S} wavenumbers set (set_wavenumbers): use "
+                                     "solve_wavenumbers(points, k, sources=...), or clear them with "
+                                     "set_wavenumbers(None)")
                 s = np.zeros((n, 2 * S + 1), np.float64)
                 wv = np.empty(n * nWalks * S, np.float32) if want_walks else None
                 ws = np.empty(n * nWalks, np.uint32) if want_walks else None
@@ -494,6 +505,120 @@ class WostSolver_2D:
         step counts, uint32 [N, nWalks] (shared by all sources)."""
         _, vals, steps = self._solve_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, True)
         return np.concatenate(vals, axis=0), steps
+
+
+
+    # ---- 2.5-D wavenumber batching (DESIGN.md, include/wost.h wost_set_wavenumbers) ---------
+    def set_wavenumbers(self, k=None):
+        """Score the screened problems div(alpha grad u) - k^2 alpha u = -f of the
+        wavenumbers ``k`` (an array of k >= 0, not squared) with every walk, or none
+        (``None`` or empty: the solver's own PDE). Needs delta tracking (alpha or sigma
+        given; a constant alpha is enough) and at most WOST_MAX_SOURCES channels
+        (wavenumbers x sources) per launch; ``solve_wavenumbers`` chunks larger requests.
+        ``solve`` / ``solve_walks`` keep working with one wavenumber set. The collision
+        weights are 1 - (sigma' + k^2)/sigma_bar: create the solver with
+        ``sigma_bar >= max sigma' + max k^2`` (``wavenumber.sigma_bar_for``)."""
+        kk = np.zeros(0) if k is None else np.atleast_1d(np.asarray(k, np.float64)).ravel()
+        # (squaring would hide a negative k: it, and NaN, reach the library as invalid)
+        k2 = np.ascontiguousarray(np.where(kk >= 0, kk * kk, -1.0), dtype=np.float64)
+        _lib.check(_lib.lib.wost_set_wavenumbers(self._h, _lib.dptr(k2) if k2.size else None, int(k2.size)),
+                   "WostSolver_2D.set_wavenumbers")
+        self.wavenumbers = kk.copy() if kk.size else None
+
+    def num_channels(self) -> int:
+        n = ctypes.c_int32(1)
+        _lib.check(_lib.lib.wost_num_channels(self._h, ctypes.byref(n)), "wost_num_channels")
+        return int(n.value)
+
+    def _solve_channels(self, solvePoints, k, sources, nWalks, maxSteps, eps, seed, want_walks):
+        """One launch per (source chunk, wavenumber chunk) of at most WOST_MAX_SOURCES
+        channels: rows [Kc][Sc] of point sums [N, 3] and (want_walks) per-walk values
+        [Kc, Sc, N, W]; the solver's wavenumbers and source are restored afterwards."""
+        p = _points_np(solvePoints)
+        n = p.shape[0]
+        nWalks = int(nWalks)
+        if nWalks < 1:
+            raise ValueError("nWalks must be >= 1")
+        kk = np.atleast_1d(np.asarray(k, np.float64)).ravel()
+        if kk.size < 1:
+            raise ValueError("k must hold at least one wavenumber")
+        fields = None if sources is None else self.source_fields(sources)
+        S = 1 if fields is None else len(fields)
+        K = kk.size
+        nb = self.num_blocks(n, nWalks)
+        s_chunk = min(S, _lib.WOST_MAX_SOURCES)
+        k_chunk = max(1, _lib.WOST_MAX_SOURCES // s_chunk)
+        sums = np.zeros((K, S, n, 3), np.float64)
+        vals = np.empty((K, S, n, nWalks), np.float32) if want_walks else None
+        steps = None
+        total = None   # the launches' timings summed (the launch shape: the last launch's)
+        saved = self.wavenumbers
+        self.set_wavenumbers(None)   # (wost_set_sources checks sources x wavenumbers)
+        try:
+            for s0 in range(0, S, s_chunk):
+                s1 = min(S, s0 + s_chunk)
+                ctx = contextlib.nullcontext() if fields is None else self.sources_installed(fields[s0:s1])
+                with ctx:
+                    try:
+                        for k0 in range(0, K, k_chunk):
+                            k1 = min(K, k0 + k_chunk)
+                            self.set_wavenumbers(kk[k0:k1])
+                            C = (k1 - k0) * (s1 - s0)
+                            rows = np.zeros((n, 2 * C + 1), np.float64)
+                            wv = np.empty(n * nWalks * C, np.float32) if want_walks else None
+                            ws = np.empty(n * nWalks, np.uint32) if want_walks else None
+                            _lib.check(_lib.lib.wost_solve_multi(self._h, _lib.fptr(p), n, nWalks, 0, nb, int(maxSteps),
+                                                                 float(eps), int(seed) & (2**64 - 1), None,
+                                                                 _lib.dptr(rows), _lib.fptr(wv), _lib.u32ptr(ws)),
+                                       "WostSolver_2D.solve_wavenumbers")
+                            t = self.timing()
+                            if total is not None:
+                                for key in _SUMMED_TIMINGS:
+                                    t[key] += total[key]
+                            self.last_timing = total = t
+                            r = rows[:, :2 * C].reshape(n, k1 - k0, s1 - s0, 2)
+                            sums[k0:k1, s0:s1, :, :2] = r.transpose(1, 2, 0, 3)
+                            sums[k0:k1, s0:s1, :, 2] = rows[:, -1]
+                            if want_walks:
+                                vals[k0:k1, s0:s1] = wv.reshape(n, nWalks, k1 - k0, s1 - s0).transpose(2, 3, 0, 1)
+                                steps = ws.reshape(n, nWalks)
+                    finally:
+                        self.set_wavenumbers(None)
+        finally:
+            self.set_wavenumbers(saved)
+        return sums, vals, steps
+
+    def solve_wavenumbers(self, solvePoints, k, nWalks=1000, maxSteps=1000, eps=1e-4, *, sources=None,
+                          seed: int = 0, return_stats: bool = False):
+        """2.5-D wavenumber batching: u[j] solves div(alpha grad u) - k[j]^2 alpha u = -f
+        (this solver's PDE with the absorption sigma + k^2 alpha), every wavenumber -- and
+        with ``sources`` every source -- scored by the same walks: under delta tracking a
+        walk's path depends only on sigma_bar. Each u[j] (u[j, s]) is bit for bit the single
+        solve of (k[j], sources[s]) with the same seed. Returns float32 [K, N], or
+        [K, S, N] with ``sources``; with ``return_stats`` also a SolveStats whose mean and
+        stderr have that shape. More than WOST_MAX_SOURCES channels are solved in several
+        launches, and ``last_timing`` / the stats' kernel_ms and total_ms then sum over them.
+        The solver's wavenumbers and source are restored afterwards."""
+        sums, _, _ = self._solve_channels(solvePoints, k, sources, nWalks, maxSteps, eps, seed, False)
+        K, S, n = sums.shape[:3]
+        st = stats_from_sums(sums.reshape(K * S * n, 3), int(nWalks))
+        shape = (K, n) if sources is None else (K, S, n)
+        u = st.mean.astype(np.float32).reshape(shape)
+        if not return_stats:
+            return u
+        t = self.last_timing
+        return u, SolveStats(mean=st.mean.reshape(shape), stderr=st.stderr.reshape(shape),
+                             mean_steps=sums[0, 0, :, 2] / int(nWalks), walks=int(nWalks),
+                             total_steps=int(sums[0, 0, :, 2].sum()), kernel_ms=t["walk_kernel_ms"],
+                             total_ms=t["total_ms"])
+
+    def solve_wavenumbers_walks(self, solvePoints, k, nWalks=1000, maxSteps=1000, eps=1e-4, *, sources=None,
+                                seed: int = 0):
+        """Per-walk values of every wavenumber (and source), float32 [K, N, nWalks] or
+        [K, S, N, nWalks], and the walks' step counts, uint32 [N, nWalks] (shared by all
+        channels: the paths do not depend on them)."""
+        _, vals, steps = self._solve_channels(solvePoints, k, sources, nWalks, maxSteps, eps, seed, True)
+        return (vals[:, 0] if sources is None else vals), steps
 
 
 def _stats_of_multi(sums: np.ndarray, n_walks: int):

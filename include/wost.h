@@ -283,6 +283,35 @@ int wost_solve_multi(wost_handle* h, const float* points, int64_t n_points,
                      double* block_stats, double* point_stats,
                      float* walk_values, uint32_t* walk_steps);
 
+/* 2.5-D wavenumber batching (no reference counterpart). A DC survey over 2-D geology with
+ * point electrodes Fourier-transforms along strike and solves, per wavenumber k,
+ *      div(alpha grad u_k) - k^2 alpha u_k = -f,
+ * this solver's PDE with the absorption sigma + k^2 alpha. Under delta tracking a walk's path
+ * depends only on sigma_bar, and sigma' = (sigma + k^2 alpha)/alpha + ... = sigma'_0 + k^2
+ * enters only through the collision weight 1 - sigma'/sigma_bar, so one walk scores every
+ * wavenumber: wost_set_wavenumbers gives the handle n values k2[j] = k_j^2 (n = 0 clears
+ * them), and its solves then score C = n * wost_num_sources channels per walk, channel
+ * c = j * S + s (wavenumber j major, source s minor). wost_solve_multi, wost_solve_range and
+ * wost_solve_distributed take C wherever they document S: rows of 2C+1 doubles,
+ * walk_values [walks][C]. Each channel's sums are bit for bit those of a single solve of
+ * (k2[j], source s); k2 = {0} gives the bits of a handle without wavenumbers. wost_solve and
+ * wost_solve_history need C == 1 (a single k2 is fine). n > 1 needs the field-specialised
+ * kernel, as S > 1 does; the kernel reads k2 at run time, so one compiled kernel per
+ * (problem, S, n) serves every set of values.
+ *   WOST_ERR_INVALID_ARG  a k2[j] that is negative or not finite, or n * S > WOST_MAX_SOURCES
+ *                         (wost_set_sources checks the same product);
+ *   WOST_ERR_UNSUPPORTED  a handle without delta tracking (neither sigma nor alpha given): give
+ *                         alpha -- a constant alpha is enough.
+ * sigma_bar is fixed at wost_create (the sampler tables depend on it), and its estimate is the
+ * RANGE of sigma' on the reference's grid (max - min, quirk Q8), which adding k^2 does not
+ * change: for collision weights in [0, 1] create the handle with sigma_bar_override >=
+ * max sigma' + max k2 (the Python facade's sigma_bar_for computes it). compat="reference"
+ * clamps each channel's weight at 0 as the reference does; compat="fixed" keeps it signed
+ * (unbiased for any sigma_bar, at a higher variance when the bound is violated). */
+int wost_set_wavenumbers(wost_handle* h, const double* k2, int32_t n);
+/* Values a solve of the handle scores per walk: max(1, wavenumbers) * wost_num_sources. */
+int wost_num_channels(const wost_handle* h, int32_t* n_channels);
+
 int wost_last_timing(const wost_handle* h, wost_timing* out);
 
 /* Number of source fields the handle scores (1, or n of wost_set_sources). */
@@ -490,6 +519,12 @@ int wost_kernel_source(const wost_problem* problem, char* out, int64_t capacity,
  * default; option param_sources = 1 reads them from the program buffer instead). */
 int wost_kernel_source_sources(const wost_problem* problem, const wost_field* const* sources, int32_t n_sources,
                                char* out, int64_t capacity, int64_t* length);
+
+/* The same for n_wavenumbers wavenumbers on top (wost_set_wavenumbers; 0: none, as
+ * wost_kernel_source_sources), so that a machine without a GPU can generate and compile the
+ * multi-wavenumber kernel. */
+int wost_kernel_source_channels(const wost_problem* problem, const wost_field* const* sources, int32_t n_sources,
+                                int32_t n_wavenumbers, char* out, int64_t capacity, int64_t* length);
 
 /* Compiles a generated walk-kernel source (wost_kernel_source) for the gfx target `arch`
  * ("gfx950") with the compile options of a new handle, without a device: in the compile

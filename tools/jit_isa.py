@@ -4,7 +4,7 @@
 Generates the kernel source libwost would hand to hiprtc (wost_kernel_source),
 compiles it with hipcc for gfx950 with hiprtc's options, and prints the
 kernel's resource usage and an instruction histogram (static counts).
-Usage: python tools/jit_isa.py dcr_dipole [--out build/jit] [--show]"""
+Usage: python tools/jit_isa.py dcr_dipole [--out build/jit] [--show] [--wavenumbers NK] [--sources NS]"""
 import argparse
 import collections
 import os
@@ -22,6 +22,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "build", "jit"))
     ap.add_argument("--show", action="store_true", help="print the ISA")
     ap.add_argument("--waves", default=None, help="WOST_JIT_WAVES for the generator")
+    ap.add_argument("--wavenumbers", type=int, default=0, help="NK: wavenumbers per walk (set_wavenumbers; 0: none)")
+    ap.add_argument("--sources", type=int, default=0, help="NS: copies of the scenario's source (solve_sources; 0: its own)")
     a = ap.parse_args()
     if a.waves:
         os.environ["WOST_JIT_WAVES"] = a.waves
@@ -30,12 +32,14 @@ def main():
     kw = {"n_walks": 1}
     sc = S.ALL[a.scenario](**({"n_electrodes": 4} if a.scenario in ("dcr_dipole", "wenner_topography") else {}), **kw) \
         if a.scenario in ("dcr_dipole", "wenner_topography") else S.ALL[a.scenario]()
-    src = sc.kernel_source()
+    src = sc.kernel_source(n_wavenumbers=a.wavenumbers, **({"sources": [sc.f * (1.0 + k) for k in range(a.sources)]}
+                                                           if a.sources else {}))
     os.makedirs(a.out, exist_ok=True)
-    hip = os.path.join(a.out, f"{a.scenario}.hip")
+    tag = a.scenario + (f"_nk{a.wavenumbers}" if a.wavenumbers else "") + (f"_ns{a.sources}" if a.sources else "")
+    hip = os.path.join(a.out, f"{tag}.hip")
     with open(hip, "w") as f:
         f.write(src)
-    asm = os.path.join(a.out, f"{a.scenario}.s")
+    asm = os.path.join(a.out, f"{tag}.s")
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--offload-device-only", "-S", "-O3", "-std=c++17",
            "-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=fast-honor-pragmas",
            *([] if os.environ.get("WOST_JIT_SLP") == "1" else ["-fno-slp-vectorize"]),
