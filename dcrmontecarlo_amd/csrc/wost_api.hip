@@ -22,6 +22,7 @@
 #include "wost_device.h"
 #include "wost_internal.h"
 #include "wost_jit.h"
+#include "wost_launch.h"
 #include "wost_options.h"
 #include "wost_tables.h"
 #include "wost_tree.h"
@@ -251,6 +252,7 @@ struct wost_handle {
     char* h_pin = nullptr;
     size_t pin_cap = 0;
     bool counter_zero = false;        // d_counter is 0 (the block reduce resets it after each walk launch)
+    Batch batch;                      // the current launch's plan (wost_launch.h; its block list is reused)
     wost_timing timing{};
 };
 
@@ -928,18 +930,53 @@ namespace {
 
 constexpr int64_t kMaxRecordBatchBytes = int64_t(1) << 30;   // device buffer of the walk recorder
 
-// wost_solve, and with `records` != null also the walk recorder
-// (wost_solve_history): records[walk][max_steps + 1][kRecFloats] on the host.
-// Walk-range mode (wost_solve_range): walk_begin/walk_end != 0/W solves walks
-// [walk_begin, walk_end) of every point; blocks are then (point, block of the
-// range), point-major, and block_begin/block_end are ignored.
+// What a solve computes: W walks of each point, of which either blocks [block_begin,
+// block_end) or (wost_solve_range) walks [walk_begin, walk_end) of every point
+// (wost_launch.h SolveRanges). multi: the caller takes channels() values per walk.
+struct SolveRequest {
+    const float* points = nullptr;
+    int64_t n_points = 0, W = 0;
+    int32_t max_steps = 0;
+    float eps = 0.f;
+    uint64_t seed = 0;
+    bool multi = false;
+    int64_t block_begin = 0, block_end = 0;
+    int64_t walk_begin = 0, walk_end = -1;   // (-1: W)
+};
+
+// Where its results go on the host (each may be null): rows of 2 * channels + 1 doubles per
+// block and per point, per-walk values and steps, and with `records` the walk recorder's
+// (wost_solve_history) records[walk][max_steps + 1][kRecFloats].
+struct SolveOutputs {
+    double* block_stats = nullptr;
+    double* point_stats = nullptr;
+    float* walk_values = nullptr;
+    uint32_t* walk_steps = nullptr;
+    float* records = nullptr;
+};
+
+SolveRequest whole_request(const float* points, int64_t n_points, int64_t W, int32_t max_steps, float eps,
+                           uint64_t seed) {
+    SolveRequest rq;
+    rq.points = points;
+    rq.n_points = n_points;
+    rq.W = W;
+    rq.max_steps = max_steps;
+    rq.eps = eps;
+    rq.seed = seed;
+    rq.block_end = wost_num_blocks(n_points, W);
+    return rq;
+}
+
 // The kernel a solve of n_points launches first (its occupancy fallback may then stage
 // less): the workgroup, the segment tree's staging, and whether the polylines are read
-// from global memory. Shared by solve_impl and wost_prepare_multi, so that a prepared
-// kernel is the one the solve looks up.
+// from global memory. Shared by choose_kernel, solve_race and wost_prepare_sources, so that
+// a raced or prepared kernel is the one the solve looks up.
 struct KernelShape {
     int block = kWalkBlock, tree_verts = 0, tree_level = kTreeLdsDefaultLevel, tree_lds = 0;
     bool gpoly = false;
+    // the staging level compiled into the kernel (tree_lds_records)
+    int stage() const { return tree_lds > 0 ? (tree_verts > 0 ? 2 : 1) : 0; }
 };
 
 int first_kernel_shape(const wost_handle* h, int mode, int64_t n_points, KernelShape* ks) {
@@ -971,48 +1008,105 @@ int first_kernel_shape(const wost_handle* h, int mode, int64_t n_points, KernelS
     return WOST_OK;
 }
 
-int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t block_begin,
-               int64_t block_end, int32_t max_steps, float eps, uint64_t seed, double* block_stats,
-               double* point_stats, float* walk_values, uint32_t* walk_steps, float* records, bool multi = false,
-               int64_t walk_begin = 0, int64_t walk_end = -1) {
-    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+// The kernel a solve launches and how it fits a CU.
+struct KernelChoice {
+    hipFunction_t jfn = nullptr;   // the field-specialised kernel; null: the precompiled one
+    int block = kWalkBlock, tree_lds = 0, tree_verts = 0;
+    bool gpoly = false;
+    size_t lds = 0;                // dynamic LDS of a workgroup
+    int blocks_per_cu = 0;
+    double jit_ms = 0.0;           // host time spent compiling
+};
+
+// LDS bytes per workgroup of the chosen kernel
+size_t lds_of(const wost_handle* h, int mode, int64_t n_points, const KernelChoice& kc) {
+    const int nd_ = (int)(h->dverts.size() / 2), nn_ = (int)(h->nverts.size() / 2);
+    const bool jit = kc.jfn != nullptr;
+    // option lds_pad_bytes (occupancy studies): extra bytes of LDS per workgroup
+    return walk_lds_bytes(mode, nd_, nn_, (int)n_points, kc.tree_lds, jit && jit_const_dirichlet(h->opt, nd_),
+                          jit && jit_const_neumann(h->opt, mode, nn_), jit && kc.gpoly, kc.block, kc.tree_verts) +
+           (size_t)h->opt.lds_pad_bytes;
+}
+
+// The kernel of a solve of n_points with the handle's fields: the field-specialised one of
+// first_kernel_shape, staging less of the segment tree while what it stages costs the CU
+// its waves; the precompiled one when that is disabled or could not be built.
+int choose_kernel(wost_handle* h, int mode, int64_t n_points, bool record, int n_src, int ns, KernelChoice* kc) {
+    *kc = KernelChoice{};
+    KernelShape ks;
+    int rc;
+    if ((rc = first_kernel_shape(h, mode, n_points, &ks)) != WOST_OK) return rc;
+    kc->gpoly = ks.gpoly;
+    int lds_cap = -1;
+    // looks ks up and measures its occupancy
+    auto lookup = [&]() -> int {
+        kc->jfn = jit_kernel(h, mode, record, n_src, ks.block, ks.gpoly, ks.stage(), &kc->jit_ms);
+        if (!kc->jfn) {   // the precompiled kernels run 256-thread workgroups, no staged tree, one channel
+            if (ns > 1)
+                return fail(WOST_ERR_UNSUPPORTED,
+                            "multi-source and multi-wavenumber solves need the field-specialised kernel%s%s",
+                            h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
+            ks.block = kWalkBlock;
+            ks.tree_lds = ks.tree_verts = 0;
+        }
+        kc->block = ks.block;
+        kc->tree_lds = ks.tree_lds;
+        kc->tree_verts = ks.tree_verts;
+        kc->lds = lds_of(h, mode, n_points, *kc);
+        kc->blocks_per_cu = 0;
+        if (lds_cap < 0)
+            HIP_TRY(hipDeviceGetAttribute(&lds_cap, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device));
+        // a workgroup whose LDS exceeds the CU's never fits: checked here, not left to the
+        // occupancy query
+        if (kc->jfn && kc->lds <= (size_t)lds_cap)
+            HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&kc->blocks_per_cu, kc->jfn, kc->block, kc->lds));
+        return WOST_OK;
+    };
+    if ((rc = lookup()) != WOST_OK) return rc;
+    while (kc->jfn && ks.tree_lds > 0 && kc->blocks_per_cu * (ks.block / 64) < 16) {
+        // what the tree stages leaves fewer than 16 waves per CU (or does not fit at all):
+        // stage less (the vertices, then the records), down to reading both through L1/L2
+        // from 256-thread workgroups
+        ks.tree_level = ks.tree_verts > 0 ? 1 : 0;
+        ks.tree_lds = tree_lds_records(h, mode, ks.tree_level, &ks.block, &ks.tree_verts);
+        if ((rc = lookup()) != WOST_OK) return rc;
+    }
+    if (!kc->jfn)
+        HIP_TRY(walk_occupancy(mode, (int)(h->dverts.size() / 2), (int)(h->nverts.size() / 2), (int)n_points,
+                               &kc->blocks_per_cu));
+    if (kc->blocks_per_cu < 1)
+        return fail(WOST_ERR_UNSUPPORTED, "walk kernel does not fit on a CU (polylines too large for LDS: %zu bytes)",
+                    kc->lds);
+    return WOST_OK;
+}
+
+// The argument checks of a solve, its ranges, and the compat="fixed" step-count refusal.
+int check_request(const wost_handle* h, const SolveRequest& rq, SolveRanges* ranges) {
     const int n_src = h->n_sources;
     const int ns = h->channels();   // values per walk: channel c = j * n_src + s (wavenumber j, source s)
-    if (ns != 1 && !multi)
+    const float* points = rq.points;
+    const int64_t n_points = rq.n_points, W = rq.W;
+    if (ns != 1 && !rq.multi)
         return fail(WOST_ERR_INVALID_ARG,
                     "the handle scores %d channels (%d sources of wost_set_sources x %d wavenumbers of "
                     "wost_set_wavenumbers): use wost_solve_multi", ns, n_src, ns / n_src);
-    const int row = 2 * ns + 1;   // doubles per block / point row
     if (n_points < 0 || (n_points > 0 && !points)) return fail(WOST_ERR_INVALID_ARG, "bad points");
     if (W <= 0) return fail(WOST_ERR_INVALID_ARG, "nWalks must be >= 1 (got %lld)", (long long)W);
-    if (max_steps < 0) return fail(WOST_ERR_INVALID_ARG, "maxSteps must be >= 0");
-    if (!(eps == eps)) return fail(WOST_ERR_INVALID_ARG, "eps is NaN");
+    if (rq.max_steps < 0) return fail(WOST_ERR_INVALID_ARG, "maxSteps must be >= 0");
+    if (!(rq.eps == rq.eps)) return fail(WOST_ERR_INVALID_ARG, "eps is NaN");
     if (n_points > 0 && W > (int64_t(1) << 53) / n_points)
         return fail(WOST_ERR_INVALID_ARG, "n_points * nWalks must stay below 2^53 walks");
-    const int64_t nbpp = (W + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
-    const int64_t nb_total = n_points * nbpp;
-    if (walk_end < 0) walk_end = W;
-    const bool range = walk_begin != 0 || walk_end != W;
-    if (range && (walk_begin < 0 || walk_end <= walk_begin || walk_end > W || walk_begin % WOST_BLOCK_WALKS != 0 ||
-                  (walk_end % WOST_BLOCK_WALKS != 0 && walk_end != W)))
-        return fail(WOST_ERR_INVALID_ARG,
-                    "walk range [%lld,%lld) of %lld walks must be non-empty with block-aligned ends (multiples of %d, "
-                    "or the end at W)", (long long)walk_begin, (long long)walk_end, (long long)W, WOST_BLOCK_WALKS);
-    const int64_t Wr = walk_end - walk_begin;                            // walks per point solved
-    const int64_t nbr = (Wr + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;   // blocks per point solved
-    if (range) {
-        block_begin = 0;
-        block_end = n_points * nbr;
-    } else if (block_begin < 0 || block_end < block_begin || block_end > nb_total)
-        return fail(WOST_ERR_INVALID_ARG, "block range [%lld,%lld) outside [0,%lld)", (long long)block_begin,
-                    (long long)block_end, (long long)nb_total);
+    char msg[512];
+    if (int rc = plan_ranges(n_points, W, rq.block_begin, rq.block_end, rq.walk_begin, rq.walk_end, ranges, msg,
+                             sizeof(msg)))
+        return fail(rc, "%s", msg);
     for (int64_t i = 0; i < 2 * n_points; ++i)
         if (!std::isfinite(points[i])) return fail(WOST_ERR_INVALID_ARG, "solve point %lld is not finite", (long long)(i / 2));
     if (h->delta && !h->fields[SLOT_F].present)
         return fail(WOST_ERR_INVALID_ARG,
                     "delta tracking (sigma/alpha given) needs a source term: the reference raises "
                     "UnboundLocalError at solvers/WoStSolver.py:281 (quirk Q14)");
-    if (h->compat == WOST_COMPAT_FIXED && h->delta && h->fixed_step_check && n_points > 0 && max_steps > 0 &&
+    if (h->compat == WOST_COMPAT_FIXED && h->delta && h->fixed_step_check && n_points > 0 && rq.max_steps > 0 &&
         h->dverts.size() >= 4) {
         // compat="fixed" delta tracking draws each collision from the ball's own screened
         // law: with R sqrt(sigma_bar) >> 1 a step moves ~2/sqrt(sigma_bar) (E[l^2] = 4 /
@@ -1028,153 +1122,54 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
         }
         std::nth_element(est.begin(), est.begin() + n_points / 2, est.end());
         const double med = est[(size_t)(n_points / 2)];
-        if (med > (double)max_steps)
+        if (med > (double)rq.max_steps)
             return fail(WOST_ERR_INVALID_ARG,
                         "compat=\"fixed\" delta tracking would truncate the walks: at the median query point a walk "
                         "needs ~%.3g steps (d^2 sigma_bar / 4, sigma_bar = %g) to reach the Dirichlet boundary, "
                         "maxSteps is %d; raise maxSteps, lower sigma_bar, or disable this check "
                         "(wost_set_fixed_step_check / WostSolver_2D.set_fixed_step_check(False))",
-                        med, h->sigma_bar, (int)max_steps);
+                        med, h->sigma_bar, (int)rq.max_steps);
     }
-    const int mode = walk_mode(h);
-    const bool src = h->fields[SLOT_F].present;
+    return WOST_OK;
+}
 
-    HIP_TRY(hipSetDevice(h->device));
-    int rc;
-    if ((rc = upload_program(h)) != WOST_OK) return rc;
-    if (src && (rc = ensure_table(h)) != WOST_OK) return rc;
-    if (mode_tree(mode) && (rc = ensure_tree(h)) != WOST_OK) return rc;
+// Pinned staging: [points | one batch's block ranges | the block sums], 64-byte aligned;
+// the device holds the first two parts in one buffer of the same layout (h->d_points,
+// h->d_begin), so that one copy brings the points and the first batch's block ranges (C2: a
+// copy and its ~6 us gap less)
+struct Staging {
+    float* points = nullptr;
+    int64_t* begin = nullptr;
+    double* bstats = nullptr;
+    size_t pts_bytes = 0, beg_bytes = 0, bs_bytes = 0;
+};
 
-    h->timing = wost_timing{};
-    const int64_t nblk = block_end - block_begin;
-    if (point_stats) std::fill(point_stats, point_stats + row * n_points, 0.0);
-    if (nblk == 0) return WOST_OK;
-
-    // block -> global walk range
-    auto blk_begin = [&](int64_t j) { return (j / nbpp) * W + (j % nbpp) * WOST_BLOCK_WALKS; };
-    auto blk_end = [&](int64_t j) {
-        const int64_t p = j / nbpp, b = j % nbpp;
-        return p * W + std::min<int64_t>((b + 1) * WOST_BLOCK_WALKS, W);
-    };
-
-    const int64_t walks_total = range ? n_points * Wr : blk_end(block_end - 1) - blk_begin(block_begin);
-    // walks per launch: the recorder's device buffer bounds it
-    int64_t batch_limit = kMaxBatchWalks / ns;
-    const int64_t rec_stride = (int64_t)max_steps + 1;
-    const int64_t rec_walk_bytes = rec_stride * kRecFloats * (int64_t)sizeof(float);
-    if (records) {
-        batch_limit = std::min<int64_t>(kMaxBatchWalks, kMaxRecordBatchBytes / rec_walk_bytes);
-        if (batch_limit < std::min<int64_t>(W, WOST_BLOCK_WALKS))
-            return fail(WOST_ERR_INVALID_ARG,
-                        "return_history: %lld recorded steps per walk need more than %lld bytes per walk block; "
-                        "lower maxSteps or nWalks", (long long)rec_stride, (long long)kMaxRecordBatchBytes);
-    }
-    if (range && Wr > batch_limit)
-        return fail(WOST_ERR_INVALID_ARG, "walk range of %lld walks per point exceeds one launch (%lld walks)",
-                    (long long)Wr, (long long)batch_limit);
-    // pinned staging: [points | one batch's block ranges | the block sums], 64-byte aligned;
-    // the device holds the first two parts in one buffer of the same layout, so that one copy
-    // brings the points and the first batch's block ranges (C2: a copy and its ~6 us gap less)
+int stage_buffers(wost_handle* h, int64_t n_points, int64_t nblk, int row, Staging* st) {
     auto al64 = [](size_t b) { return (b + 63) / 64 * 64; };
-    const size_t pin_pts = al64(sizeof(float2) * (size_t)std::max<int64_t>(n_points, 1));
-    const size_t pin_beg = al64(sizeof(int64_t) * (size_t)(nblk + 1));
-    const size_t pin_bs = al64(sizeof(double) * (size_t)(kLstatsWords + row * nblk));
-    if ((rc = ensure_pin(h, pin_pts + pin_beg + pin_bs)) != WOST_OK) return rc;
-    if (pin_pts + pin_beg > h->stage_cap) {
+    st->pts_bytes = al64(sizeof(float2) * (size_t)std::max<int64_t>(n_points, 1));
+    st->beg_bytes = al64(sizeof(int64_t) * (size_t)(nblk + 1));
+    st->bs_bytes = al64(sizeof(double) * (size_t)(kLstatsWords + row * nblk));
+    const size_t dev_bytes = st->pts_bytes + st->beg_bytes;
+    if (int rc = ensure_pin(h, dev_bytes + st->bs_bytes)) return rc;
+    if (dev_bytes > h->stage_cap) {
         if (h->d_stage) (void)hipFree(h->d_stage);
         h->d_stage = nullptr;
         h->stage_cap = 0;
-        const hipError_t e = hipMalloc(&h->d_stage, pin_pts + pin_beg);
-        if (e != hipSuccess)
-            return fail(WOST_ERR_OOM, "hipMalloc(%zu bytes): %s", pin_pts + pin_beg, hipGetErrorString(e));
-        h->stage_cap = pin_pts + pin_beg;
+        const hipError_t e = hipMalloc(&h->d_stage, dev_bytes);
+        if (e != hipSuccess) return fail(WOST_ERR_OOM, "hipMalloc(%zu bytes): %s", dev_bytes, hipGetErrorString(e));
+        h->stage_cap = dev_bytes;
     }
     h->d_points = reinterpret_cast<float2*>(h->d_stage);
-    h->d_begin = reinterpret_cast<int64_t*>(h->d_stage + pin_pts);
-    float* const pin_points = reinterpret_cast<float*>(h->h_pin);
-    int64_t* const pin_begin = reinterpret_cast<int64_t*>(h->h_pin + pin_pts);
-    double* const pin_bstats = reinterpret_cast<double*>(h->h_pin + pin_pts + pin_beg);
-    std::memcpy(pin_points, points, sizeof(float2) * (size_t)n_points);
-    // the points go with the first batch's block ranges, unless the query points' alpha
-    // (delta tracking) needs them first
-    bool points_pending = true;
-    if (mode_delta(mode) && n_points > 0) {
-        HIP_TRY(hipMemcpyAsync(h->d_points, pin_points, sizeof(float2) * n_points, hipMemcpyHostToDevice, h->stream));
-        points_pending = false;
-    }
-    if ((rc = ensure_workspace(h, std::min<int64_t>(walks_total, batch_limit), ns)) != WOST_OK) return rc;
-    if ((rc = ensure_cap(h->d_bstats, h->bstats_cap, kLstatsWords + nblk * row)) != WOST_OK) return rc;
-    // (the launch statistics in front of the block sums: one copy brings both)
-    unsigned long long* const d_lstats = reinterpret_cast<unsigned long long*>(h->d_bstats);
-    double* const d_rows = h->d_bstats + kLstatsWords;
-    float* d_rec = nullptr;
-    struct RecFree {
-        float*& p;
-        ~RecFree() { if (p) (void)hipFree(p); }
-    } rec_free{d_rec};
-    if (records) HIP_TRY(hipMalloc(&d_rec, (size_t)std::min<int64_t>(walks_total, batch_limit) * rec_walk_bytes));
+    h->d_begin = reinterpret_cast<int64_t*>(h->d_stage + st->pts_bytes);
+    st->points = reinterpret_cast<float*>(h->h_pin);
+    st->begin = reinterpret_cast<int64_t*>(h->h_pin + st->pts_bytes);
+    st->bstats = reinterpret_cast<double*>(h->h_pin + dev_bytes);
+    return WOST_OK;
+}
 
-    KernelShape ks;
-    if ((rc = first_kernel_shape(h, mode, n_points, &ks)) != WOST_OK) return rc;
-    int block = ks.block, tree_verts = ks.tree_verts, tree_level = ks.tree_level, tree_lds = ks.tree_lds;
-    bool gpoly = ks.gpoly;
-    const int nd_ = (int)(h->dverts.size() / 2), nn_ = (int)(h->nverts.size() / 2);
-    const Options& O = h->opt;
-    double jit_ms = 0.0;
-    auto stage_of = [](int recs, int verts) { return recs > 0 ? (verts > 0 ? 2 : 1) : 0; };
-    hipFunction_t jfn = jit_kernel(h, mode, records != nullptr, n_src, block, gpoly, stage_of(tree_lds, tree_verts),
-                                   &jit_ms);
-    if (!jfn && block != kWalkBlock) {   // the precompiled kernels run 256-thread workgroups, no staged tree
-        block = kWalkBlock;
-        tree_lds = 0;
-        tree_verts = 0;
-    }
-    if (ns > 1 && !jfn)
-        return fail(WOST_ERR_UNSUPPORTED, "multi-source and multi-wavenumber solves need the field-specialised kernel%s%s",
-                    h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
-    size_t lds = walk_lds_bytes(mode, nd_, nn_, (int)n_points, tree_lds, jfn && jit_const_dirichlet(O, nd_),
-                                jfn && jit_const_neumann(O, mode, nn_), jfn && gpoly, block, tree_verts);
-    // option lds_pad_bytes (occupancy studies): extra bytes of LDS per workgroup
-    lds += (size_t)O.lds_pad_bytes;
-    int blocks_per_cu = 0;
-    // a workgroup whose LDS exceeds the CU's never fits: checked here, not left to the
-    // occupancy query
-    int lds_cap = 0;
-    HIP_TRY(hipDeviceGetAttribute(&lds_cap, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device));
-    auto occupancy = [&]() -> hipError_t {
-        blocks_per_cu = 0;
-        if (lds > (size_t)lds_cap) return hipSuccess;
-        return hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, jfn, block, lds);
-    };
-    if (jfn) HIP_TRY(occupancy());
-    while (jfn && tree_lds > 0 && blocks_per_cu * (block / 64) < 16) {
-        // what the tree stages leaves fewer than 16 waves per CU (or does not fit at all):
-        // stage less (the vertices, then the records), down to reading both through L1/L2
-        // from 256-thread workgroups
-        tree_level = tree_verts > 0 ? 1 : 0;
-        tree_lds = tree_lds_records(h, mode, tree_level, &block, &tree_verts);
-        if (!(jfn = jit_kernel(h, mode, records != nullptr, n_src, block, gpoly, stage_of(tree_lds, tree_verts),
-                               &jit_ms))) {
-            // the precompiled kernels then (256-thread workgroups, nothing of the tree staged)
-            block = kWalkBlock;
-            tree_lds = tree_verts = 0;
-            if (ns > 1)
-                return fail(WOST_ERR_UNSUPPORTED,
-                            "multi-source and multi-wavenumber solves need the field-specialised kernel: %s",
-                            h->jit_error.c_str());
-            break;
-        }
-        lds = walk_lds_bytes(mode, nd_, nn_, (int)n_points, tree_lds, jit_const_dirichlet(O, nd_),
-                             jit_const_neumann(O, mode, nn_), gpoly, block, tree_verts) + (size_t)O.lds_pad_bytes;
-        HIP_TRY(occupancy());
-    }
-    if (!jfn)
-        HIP_TRY(walk_occupancy(mode, (int)(h->dverts.size() / 2), (int)(h->nverts.size() / 2), (int)n_points,
-                               &blocks_per_cu));
-    if (blocks_per_cu < 1)
-        return fail(WOST_ERR_UNSUPPORTED, "walk kernel does not fit on a CU (polylines too large for LDS: %zu bytes)",
-                    lds);
-
+// The walk kernel's arguments that hold for every launch of the solve (the batch's and the
+// launch shape's are set per launch; the pools and point_alpha by the two steps below).
+WalkArgs fill_walk_args(const wost_handle* h, const SolveRequest& rq, int mode, const KernelChoice& kc, float* d_rec) {
     WalkArgs a{};
     a.points = h->d_points;
     a.dverts = h->d_dverts;
@@ -1183,18 +1178,18 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
     a.table = h->d_table;
     a.prog = h->d_prog;
     a.counter = h->d_counter;
-    a.walks_per_point = W;
+    a.walks_per_point = rq.W;
     a.nd = (int)(h->dverts.size() / 2);
     a.nn = (int)(h->nverts.size() / 2);
-    a.max_steps = max_steps;
-    a.eps = eps;
-    a.rmin = eps / 2.0f;
-    a.key0 = (uint32_t)seed;
-    a.key1 = (uint32_t)(seed >> 32);
-    a.n_points = (int32_t)std::min<int64_t>(n_points, INT32_MAX);
-    a.inv_walks_per_point = 1.0 / (double)W;
+    a.max_steps = rq.max_steps;
+    a.eps = rq.eps;
+    a.rmin = rq.eps / 2.0f;
+    a.key0 = (uint32_t)rq.seed;
+    a.key1 = (uint32_t)(rq.seed >> 32);
+    a.n_points = (int32_t)std::min<int64_t>(rq.n_points, INT32_MAX);
+    a.inv_walks_per_point = 1.0 / (double)rq.W;
     a.rec = d_rec;
-    a.rec_stride = (int32_t)rec_stride;
+    a.rec_stride = (int32_t)((int64_t)rq.max_steps + 1);
     a.exact_trig = exact_trig_of(h) ? 1 : 0;
     for (int j = 0; j < h->n_wavenumbers; ++j) a.k2[j] = h->k2[j];   // (the rest 0)
     if (mode_tree(mode)) {
@@ -1204,103 +1199,227 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
         a.tree_tol = h->tree.tol;
         a.tree_stop2 = silhouette_stop2(a.rmin);
         a.tree_kmax = h->tree.kmax;
-        a.tree_lds_records = tree_lds;
-        a.tree_lds_verts = tree_verts;
+        a.tree_lds_records = kc.tree_lds;
+        a.tree_lds_verts = kc.tree_verts;
         a.tree_depth = h->tree.depth;
-        // walk pools (wost_walk.h): near = within pool_near (default 0.1) of the Neumann
-        // polyline's largest extent from its bounding box; tree_pool = 0 turns them off,
-        // pool_slots (default 128) walks per class and workgroup
-        // (a parked walk holds one attenuation: launches of several wavenumbers run without pools)
-        if (O.tree_pool != 0 && h->nverts.size() >= 4 && h->n_wavenumbers <= 1) {
-            float x0 = h->nverts[0], x1 = x0, y0 = h->nverts[1], y1 = y0;
-            for (size_t i = 2; i + 1 < h->nverts.size(); i += 2) {
-                x0 = std::min(x0, h->nverts[i]); x1 = std::max(x1, h->nverts[i]);
-                y0 = std::min(y0, h->nverts[i + 1]); y1 = std::max(y1, h->nverts[i + 1]);
-            }
-            const float frac = (float)O.pool_near;
-            const int slots = O.pool_slots;
-            const float m = frac * std::max(x1 - x0, y1 - y0);
-            // (study builds, tree_iter_stats: 16 counter words after each workgroup's pools)
-            const int64_t words = (int64_t)pool_wg_words(n_src, slots) + (O.tree_iter_stats ? 16 : 0);
-            if ((rc = ensure_cap(h->d_pool, h->pool_cap, words * (int64_t)blocks_per_cu * h->num_cus)) != WOST_OK)
-                return rc;
-            a.pool = h->d_pool;
-            a.pool_slots = slots;
-            a.pool_wg_words = (int32_t)words;
-            a.pool_box = make_float4(x0 - m, y0 - m, x1 + m, y1 + m);
-            if (O.tree_iter_stats)
-                HIP_TRY(hipMemsetAsync(h->d_pool, 0, sizeof(uint32_t) * (size_t)(words * blocks_per_cu * h->num_cus),
-                                       h->stream));
-            a.pool_near_waves = O.pool_near_waves;   // (0: by majority)
-        }
     }
+    return a;
+}
 
-    if (mode_delta(mode) && n_points > 0) {   // alpha at the query points, with the walk kernel's fields
-        if ((rc = ensure_cap(h->d_point_alpha, h->point_alpha_cap, n_points)) != WOST_OK) return rc;
-        if (jfn) {
-            const float2* pts = h->d_points;
-            long long n = (long long)n_points;
-            float* out = h->d_point_alpha;
-            const char* prog = h->d_prog;
-            void* args[] = {&prog, &pts, &n, &out};
-            const int grid = (int)std::min<int64_t>((n_points + 255) / 256, 4096);
-            HIP_TRY(hipModuleLaunchKernel(h->jit_alpha_fn, grid, 1, 1, 256, 1, 1, 0, h->stream, args, nullptr));
-        } else {
-            HIP_TRY(launch_point_alpha(h->d_prog, h->d_points, n_points, h->d_point_alpha, h->stream));
-        }
-        a.point_alpha = h->d_point_alpha;
+// walk pools of the tree kernels (wost_walk.h): near = within pool_near (default 0.1) of the
+// Neumann polyline's largest extent from its bounding box; tree_pool = 0 turns them off,
+// pool_slots (default 128) walks per class and workgroup
+// (a parked walk holds one attenuation: launches of several wavenumbers run without pools)
+int setup_pools(wost_handle* h, int mode, int n_src, int blocks_per_cu, WalkArgs* a) {
+    const Options& O = h->opt;
+    if (!mode_tree(mode) || O.tree_pool == 0 || h->nverts.size() < 4 || h->n_wavenumbers > 1) return WOST_OK;
+    float x0 = h->nverts[0], x1 = x0, y0 = h->nverts[1], y1 = y0;
+    for (size_t i = 2; i + 1 < h->nverts.size(); i += 2) {
+        x0 = std::min(x0, h->nverts[i]); x1 = std::max(x1, h->nverts[i]);
+        y0 = std::min(y0, h->nverts[i + 1]); y1 = std::max(y1, h->nverts[i + 1]);
     }
+    const float m = (float)O.pool_near * std::max(x1 - x0, y1 - y0);
+    // (study builds, tree_iter_stats: 16 counter words after each workgroup's pools)
+    const int64_t words = (int64_t)pool_wg_words(n_src, O.pool_slots) + (O.tree_iter_stats ? 16 : 0);
+    if (int rc = ensure_cap(h->d_pool, h->pool_cap, words * (int64_t)blocks_per_cu * h->num_cus)) return rc;
+    a->pool = h->d_pool;
+    a->pool_slots = O.pool_slots;
+    a->pool_wg_words = (int32_t)words;
+    a->pool_box = make_float4(x0 - m, y0 - m, x1 + m, y1 + m);
+    if (O.tree_iter_stats)
+        HIP_TRY(hipMemsetAsync(h->d_pool, 0, sizeof(uint32_t) * (size_t)(words * blocks_per_cu * h->num_cus), h->stream));
+    a->pool_near_waves = O.pool_near_waves;   // (0: by majority)
+    return WOST_OK;
+}
 
-    std::vector<int64_t> begins;
-    std::vector<float> ms_walk, ms_red;
+// Delta tracking: alpha at the query points, with the walk kernel's fields.
+int launch_point_alpha_for(wost_handle* h, int mode, hipFunction_t jfn, int64_t n_points, WalkArgs* a) {
+    if (!mode_delta(mode) || n_points <= 0) return WOST_OK;
+    if (int rc = ensure_cap(h->d_point_alpha, h->point_alpha_cap, n_points)) return rc;
+    if (jfn) {
+        const float2* pts = h->d_points;
+        long long n = (long long)n_points;
+        float* out = h->d_point_alpha;
+        const char* prog = h->d_prog;
+        void* args[] = {&prog, &pts, &n, &out};
+        const int grid = (int)std::min<int64_t>((n_points + 255) / 256, 4096);
+        HIP_TRY(hipModuleLaunchKernel(h->jit_alpha_fn, grid, 1, 1, 256, 1, 1, 0, h->stream, args, nullptr));
+    } else {
+        HIP_TRY(launch_point_alpha(h->d_prog, h->d_points, n_points, h->d_point_alpha, h->stream));
+    }
+    a->point_alpha = h->d_point_alpha;
+    return WOST_OK;
+}
+
+// One launch's walks (wost_launch.h next_batch) in the kernel's arguments.
+void set_batch_args(const wost_handle* h, const Batch& b, WalkArgs* a) {
+    a->wid_begin = b.wid_begin;
+    a->base_pid = b.base_pid;
+    a->base_off = b.base_off;
+    a->small32 = b.small32;
+    a->range_walks = b.range_walks;
+    a->range_offset = b.range_offset;
+    a->range_point0 = b.range_point0;
+    a->inv_range_walks = b.inv_range_walks;
+    a->out_val = h->d_val;
+    a->out_steps = h->d_steps;
+    a->count = b.count;
+}
+
+// One launch's shape (wost_launch.h launch_shape) in the kernel's arguments and wost_timing.
+void set_shape_args(wost_handle* h, const LaunchShape& s, int block, WalkArgs* a) {
+    a->chunk0 = (int32_t)s.chunk0;
+    a->queue_base = s.queue_base;
+    a->chunk = s.chunk;
+    a->chunk_share = s.chunk_share;
+    a->waves = (uint32_t)std::min<int64_t>(s.waves, INT32_MAX);
+    h->timing.blocks_per_cu = (int32_t)s.bpc;
+    h->timing.block_threads = block;
+    h->timing.chunk0 = (int32_t)s.chunk0;
+    h->timing.chunk = s.chunk;
+    h->timing.adaptive = s.adaptive ? 1 : 0;
+    h->timing.grid_blocks = s.grid;
+}
+
+// A control block (h->d_counter) that holds the records of `waves` waves.
+int ensure_control_block(wost_handle* h, int64_t waves, WalkArgs* a) {
+    if ((int64_t)ctl_words(waves) <= h->ctl_cap) return WOST_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    (void)hipFree(h->d_counter);
+    h->d_counter = nullptr;
+    h->ctl_cap = 0;
+    HIP_TRY(hipMalloc(&h->d_counter, sizeof(unsigned long long) * ctl_words(waves)));
+    HIP_TRY(hipMemset(h->d_counter, 0, sizeof(unsigned long long) * ctl_words(waves)));   // synchronous
+    h->ctl_cap = (int64_t)ctl_words(waves);
+    a->counter = h->d_counter;
+    return WOST_OK;
+}
+
+// The launch statistics (wost_kernels.hip reduce_wave_stats) in front of the block sums,
+// wall-clock ticks.
+void read_launch_stats(wost_handle* h, const double* pin_bstats) {
+    unsigned long long ls[kLstatsWords];
+    std::memcpy(ls, pin_bstats, sizeof(ls));
+    const double ms_per_tick = 1.0 / h->tick_khz;
+    h->timing.max_walk_steps = (uint32_t)std::min<unsigned long long>(ls[3], 0xFFFFFFFFull);
+    h->timing.span_ms = ls[2] > ls[0] ? (double)(ls[2] - ls[0]) * ms_per_tick : 0.0;
+    h->timing.tail_ms = ls[2] > ls[1] ? (double)(ls[2] - ls[1]) * ms_per_tick : 0.0;
+    h->timing.last_wave_ms = (double)ls[5] * ms_per_tick;
+    h->timing.last_wave_iters = (uint32_t)ls[4];
+    h->timing.max_wave_iters = (uint32_t)ls[6];
+}
+
+// Study builds (tree_iter_stats): the tree queries' loop counters, summed over the workgroups.
+int dump_tree_iter_stats(const wost_handle* h, const WalkArgs& a, int blocks_per_cu) {
+    if (!h->opt.tree_iter_stats || a.pool == nullptr) return WOST_OK;
+    const int64_t nwg = (int64_t)blocks_per_cu * h->num_cus;
+    std::vector<uint32_t> pw((size_t)(a.pool_wg_words * nwg));
+    HIP_TRY(hipMemcpy(pw.data(), a.pool, sizeof(uint32_t) * pw.size(), hipMemcpyDeviceToHost));
+    const int64_t off = a.pool_wg_words - 16;
+    double c[16] = {};
+    for (int64_t g = 0; g < nwg; ++g)
+        for (int i = 0; i < 16; ++i) c[i] += pw[(size_t)(g * a.pool_wg_words + off + i)];
+    std::fprintf(stderr, "tree_iter_stats:");
+    for (int i = 0; i < 16; ++i) std::fprintf(stderr, " %.0f", c[i]);
+    std::fprintf(stderr, "\n");
+    return WOST_OK;
+}
+
+// Every solve: checks, the kernel, then one walk launch and one block reduce per batch of
+// the plan (wost_launch.h), all on the handle's stream.
+int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    SolveRanges R;
+    int rc;
+    if ((rc = check_request(h, rq, &R)) != WOST_OK) return rc;
+    const int n_src = h->n_sources;
+    const int ns = h->channels();
+    const int row = 2 * ns + 1;   // doubles per block / point row
+    const int64_t n_points = rq.n_points;
+    const int mode = walk_mode(h);
+
+    HIP_TRY(hipSetDevice(h->device));
+    if ((rc = upload_program(h)) != WOST_OK) return rc;
+    if (h->fields[SLOT_F].present && (rc = ensure_table(h)) != WOST_OK) return rc;
+    if (mode_tree(mode) && (rc = ensure_tree(h)) != WOST_OK) return rc;
+
+    h->timing = wost_timing{};
+    if (out.point_stats) std::fill(out.point_stats, out.point_stats + row * n_points, 0.0);
+    if (R.nblk == 0) return WOST_OK;
+
+    // walks per launch: the recorder's device buffer bounds it
+    int64_t batch_limit = kMaxBatchWalks / ns;
+    const int64_t rec_stride = (int64_t)rq.max_steps + 1;
+    const int64_t rec_walk_bytes = rec_stride * kRecFloats * (int64_t)sizeof(float);
+    if (out.records) {
+        batch_limit = std::min<int64_t>(kMaxBatchWalks, kMaxRecordBatchBytes / rec_walk_bytes);
+        if (batch_limit < std::min<int64_t>(rq.W, WOST_BLOCK_WALKS))
+            return fail(WOST_ERR_INVALID_ARG,
+                        "return_history: %lld recorded steps per walk need more than %lld bytes per walk block; "
+                        "lower maxSteps or nWalks", (long long)rec_stride, (long long)kMaxRecordBatchBytes);
+    }
+    if (R.range && R.Wr > batch_limit)
+        return fail(WOST_ERR_INVALID_ARG, "walk range of %lld walks per point exceeds one launch (%lld walks)",
+                    (long long)R.Wr, (long long)batch_limit);
+
+    Staging st;
+    if ((rc = stage_buffers(h, n_points, R.nblk, row, &st)) != WOST_OK) return rc;
+    std::memcpy(st.points, rq.points, sizeof(float2) * (size_t)n_points);
+    // the points go with the first batch's block ranges, unless the query points' alpha
+    // (delta tracking) needs them first
+    bool points_pending = true;
+    if (mode_delta(mode) && n_points > 0) {
+        HIP_TRY(hipMemcpyAsync(h->d_points, st.points, sizeof(float2) * n_points, hipMemcpyHostToDevice, h->stream));
+        points_pending = false;
+    }
+    if ((rc = ensure_workspace(h, std::min<int64_t>(R.walks_total, batch_limit), ns)) != WOST_OK) return rc;
+    if ((rc = ensure_cap(h->d_bstats, h->bstats_cap, kLstatsWords + R.nblk * row)) != WOST_OK) return rc;
+    // (the launch statistics in front of the block sums: one copy brings both)
+    unsigned long long* const d_lstats = reinterpret_cast<unsigned long long*>(h->d_bstats);
+    double* const d_rows = h->d_bstats + kLstatsWords;
+    float* d_rec = nullptr;
+    struct RecFree {
+        float*& p;
+        ~RecFree() { if (p) (void)hipFree(p); }
+    } rec_free{d_rec};
+    if (out.records)
+        HIP_TRY(hipMalloc(&d_rec, (size_t)std::min<int64_t>(R.walks_total, batch_limit) * rec_walk_bytes));
+
+    KernelChoice kc;
+    if ((rc = choose_kernel(h, mode, n_points, out.records != nullptr, n_src, ns, &kc)) != WOST_OK) return rc;
+    WalkArgs a = fill_walk_args(h, rq, mode, kc, d_rec);
+    if ((rc = setup_pools(h, mode, n_src, kc.blocks_per_cu, &a)) != WOST_OK) return rc;
+    if ((rc = launch_point_alpha_for(h, mode, kc.jfn, n_points, &a)) != WOST_OK) return rc;
+
+    LaunchIn shape_in;
+    shape_in.short_walks = !mode_neu(mode);
+    shape_in.tree = mode_tree(mode);
+    shape_in.block = kc.block;
+    shape_in.blocks_per_cu = kc.blocks_per_cu;
+    shape_in.num_cus = h->num_cus;
+    shape_in.opt = &h->opt;
+    shape_in.clock_is_100mhz = h->tick_khz == 100000.0;
+
+    Batch& b = h->batch;
     HIP_TRY(hipEventRecord(h->ev[4], h->stream));
-    int64_t j = block_begin;
     int64_t walks_done = 0;
     int launches = 0;
     double walk_ms = 0.0, red_ms = 0.0;
-    while (j < block_end) {
-        int64_t j2 = j, count = 0;
-        begins.clear();
-        if (range) {
-            // whole points' ranges: local walk l is walk walk_begin + l % Wr of point p0 + l / Wr
-            const int64_t p0 = j / nbr;
-            const int64_t p1 = std::min<int64_t>(n_points, p0 + std::max<int64_t>(1, batch_limit / Wr));
-            for (int64_t p = p0; p < p1; ++p)
-                for (int64_t b = 0; b < nbr; ++b) begins.push_back((p - p0) * Wr + b * WOST_BLOCK_WALKS);
-            count = (p1 - p0) * Wr;
-            j2 = p1 * nbr;
-            a.wid_begin = 0;
-            a.range_walks = Wr;
-            a.range_offset = walk_begin;
-            a.range_point0 = p0;
-            a.inv_range_walks = 1.0 / (double)Wr;
-        } else {
-            // gather whole blocks into a batch of at most kMaxBatchWalks walks
-            const int64_t wb = blk_begin(j);
-            while (j2 < block_end && blk_end(j2) - wb <= batch_limit) {
-                begins.push_back(blk_begin(j2) - wb);
-                ++j2;
-            }
-            if (j2 == j) return fail(WOST_ERR_INVALID_ARG, "internal: block larger than a batch");
-            count = blk_end(j2 - 1) - wb;
-            a.wid_begin = wb;
-            a.base_pid = wb / W;
-            const int64_t off = wb - a.base_pid * W;
-            a.base_off = (uint32_t)std::min<int64_t>(off, INT32_MAX);
-            a.small32 = (W < (int64_t(1) << 31) && off + count < (int64_t(1) << 31)) ? 1 : 0;
-            a.range_walks = 0;
-        }
-        begins.push_back(count);
-        const int64_t nb = j2 - j;
+    for (int64_t j = R.block_begin; j < R.block_end; j = b.j2) {
+        // plan the batch: blocks [j, b.j2), b.count walks
+        if (!next_batch(R, j, batch_limit, &b)) return fail(WOST_ERR_INVALID_ARG, "internal: block larger than a batch");
+        const int64_t nb = b.j2 - j, count = b.count;
+        set_batch_args(h, b, &a);
 
+        // copy its block ranges
         // (the previous batch's copy from the staging has completed: its events were waited on)
-        std::memcpy(pin_begin, begins.data(), sizeof(int64_t) * (size_t)(nb + 1));
+        std::memcpy(st.begin, b.begins.data(), sizeof(int64_t) * (size_t)(nb + 1));
         if (points_pending) {   // points and block ranges in one copy
-            HIP_TRY(hipMemcpyAsync(h->d_stage, h->h_pin, pin_pts + sizeof(int64_t) * (size_t)(nb + 1),
+            HIP_TRY(hipMemcpyAsync(h->d_stage, h->h_pin, st.pts_bytes + sizeof(int64_t) * (size_t)(nb + 1),
                                    hipMemcpyHostToDevice, h->stream));
             points_pending = false;
         } else {
-            HIP_TRY(hipMemcpyAsync(h->d_begin, pin_begin, sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->d_begin, st.begin, sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, h->stream));
         }
         // the queue head: zeroed by the previous launch's block reduce, or here after a
         // solve that stopped between a walk launch and its reduce
@@ -1308,109 +1427,39 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
             HIP_TRY(hipMemsetAsync(h->d_counter, 0, sizeof(unsigned long long) * kCtlWords, h->stream));
         h->counter_zero = false;
 
-        a.out_val = h->d_val;
-        a.out_steps = h->d_steps;
-        a.count = count;
-        // The launch's shape is a function of this call alone (never of an earlier solve:
-        // the reference calls solve() once per script, so the first call is the one that
-        // counts). Walks without a Neumann boundary (Laplace, Poisson, delta tracking on a
-        // Dirichlet-only domain) are short (13-17 steps); those with one (C3's circle, the
-        // DCR scenarios, C5) run 17-208.
-        const bool short_walks = !mode_neu(mode);
-        // Resident workgroups: few short walks per lane (C2: 640k walks, ~1.2 per lane at
-        // full occupancy) leave the launch as long as its longest walk chains, whose steps
-        // run faster with fewer waves per SIMD: ~2 walks per lane, at least 2 workgroups per
-        // CU (C2: 8 -> 2 per CU took 0.21 -> 0.18 ms, profiles/r05_ab/grid_c2/; with the
-        // all-static first chunk below 4 per CU beat 2: 0.127 -> 0.110 ms, and 8 stays best
-        // at 4x C2's walks, profiles/r06_ab/r06s37/)
-        int64_t bpc = blocks_per_cu;
-        if (short_walks && bpc > 2)
-            bpc = std::max<int64_t>(2, std::min<int64_t>(bpc, count / ((int64_t)h->num_cus * block * 2)));
-        if (O.grid_blocks_per_cu > 0) bpc = std::max<int64_t>(1, std::min<int64_t>(blocks_per_cu, O.grid_blocks_per_cu));
-        const int64_t max_grid = bpc * h->num_cus;
-        const int64_t want = (count + block - 1) / block;
-        const int grid = (int)std::max<int64_t>(1, std::min(max_grid, want));
-        const int64_t waves = (int64_t)grid * (block / 64);
-        // The work queue (wost_walk.h): a static chunk of walks per wave (below), then
-        // chunks of the rest from one global counter. Every dequeue of that
-        // counter serialises at its address (~11-16 ns): C2's 640k walks took 34k dequeues of
-        // 19 walks, all waves hitting the counter at the launch's start, 0.60 ms for 47 us of
-        // work (profiles/r05_ab/queue_chunk/, queue_static/).
-        // - static chunks except for the segment-tree kernels: their long walks lose by them
-        //   when launches run concurrently (the C5 survey's handle pairs: a late-starting
-        //   wave still owns its 64 walks; 1.38e10 -> 1.34e10, profiles/r05_ab/queue_c5/);
-        // - the dequeue's size: max(floor, min(cap, count / (waves * 4))), floor 64 for short
-        //   walks and 1 otherwise; cap 64 walks (one per lane), 16 for the segment-tree
-        //   kernels' long walks (C5: 208 steps; a wave's last chunk is work no other wave can
-        //   take: the survey 1.42e10 -> 1.46e10, profiles/r05_ab/chunk_cap/); each wave then
-        //   raises it to the floor its measured walk rate needs (WalkArgs::adaptive).
-        // - the static first chunk: at most one walk per lane (64) for long walks; for short
-        //   ones every walk of the launch when that is at most 6 per lane (no wave dequeues at
-        //   all), else 4 per lane (256). C2's 640k walks: 313 per wave, kernel 0.176 ->
-        //   0.129 ms; 12.8M walks of Laplace / Poisson: 256, +12% / +6% (64 took one walk
-        //   per lane and left ~8k dequeues serialised at the counter; profiles/r06_ab/r06s3[12]/)
-        const int64_t per_wave = (count + waves - 1) / waves;
-        int64_t chunk0 = mode_tree(mode)  ? 0
-                         : !short_walks   ? std::min<int64_t>(64, per_wave)
-                         : per_wave <= 384 ? per_wave
-                                           : 256;
-        if (O.chunk0 >= 0) chunk0 = O.chunk0;
-        const int64_t share = std::max<int64_t>(1, std::min<int64_t>(1 << 20, count / (waves * 4)));
-        int64_t chunk_min = short_walks ? 64 : 1;
-        if (O.chunk_min >= 1) chunk_min = O.chunk_min;
-        int64_t chunk_max = mode_tree(mode) ? 16 : 64;
-        if (O.chunk_max >= 1) chunk_max = O.chunk_max;
-        a.chunk0 = (int32_t)chunk0;
-        a.queue_base = waves * chunk0;
-        a.chunk = (int)std::max<int64_t>(chunk_min, std::min<int64_t>(chunk_max, share));
-        // (a guided queue -- the last ~4 walks per lane in chunks of 64 -- measured no faster
-        // on C4 and 10-14% slower on the short-walk scenarios: profiles/r02_ab/guided_queue.log)
-        // (the waves' rate floor assumes the 100 MHz wall clock of gfx950; the segment-tree
-        // kernels keep their host-sized dequeues)
-        const bool adaptive = !mode_tree(mode) && O.adaptive_chunk != 0 && O.chunk_min < 1 && O.chunk_max < 1 && h->tick_khz == 100000.0;
-        a.chunk_share = adaptive ? (uint32_t)std::max<int64_t>(share, a.chunk) : 0u;
-        a.waves = (uint32_t)std::min<int64_t>(waves, INT32_MAX);
-        if ((int64_t)ctl_words(waves) > h->ctl_cap) {   // more waves than the control block holds
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->d_counter);
-            h->d_counter = nullptr;
-            h->ctl_cap = 0;
-            HIP_TRY(hipMalloc(&h->d_counter, sizeof(unsigned long long) * ctl_words(waves)));
-            HIP_TRY(hipMemset(h->d_counter, 0, sizeof(unsigned long long) * ctl_words(waves)));
-            h->ctl_cap = (int64_t)ctl_words(waves);
-            a.counter = h->d_counter;
-        }
-        h->timing.blocks_per_cu = (int32_t)bpc;
-        h->timing.block_threads = block;
-        h->timing.chunk0 = (int32_t)chunk0;
-        h->timing.chunk = a.chunk;
-        h->timing.adaptive = adaptive ? 1 : 0;
-        h->timing.grid_blocks = grid;
+        // shape the launch
+        shape_in.count = count;
+        const LaunchShape s = launch_shape(shape_in);
+        set_shape_args(h, s, kc.block, &a);
+        if ((rc = ensure_control_block(h, s.waves, &a)) != WOST_OK) return rc;   // (more waves than it holds)
 
+        // walk, then reduce the blocks
         HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-        if (jfn) {
+        if (kc.jfn) {
             void* args[] = {&a};
-            HIP_TRY(hipModuleLaunchKernel(jfn, grid, 1, 1, block, 1, 1, (unsigned)lds, h->stream, args, nullptr));
+            HIP_TRY(hipModuleLaunchKernel(kc.jfn, s.grid, 1, 1, kc.block, 1, 1, (unsigned)kc.lds, h->stream, args, nullptr));
         } else {
-            HIP_TRY(launch_walk(mode, a, grid, h->stream));
+            HIP_TRY(launch_walk(mode, a, s.grid, h->stream));
         }
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-        HIP_TRY(launch_block_reduce(h->d_val, h->d_steps, h->d_begin, nb, ns, d_rows + row * (j - block_begin),
-                                    h->d_counter, h->stream, mode_tree(mode) ? 0 : waves, d_lstats,
+        HIP_TRY(launch_block_reduce(h->d_val, h->d_steps, h->d_begin, nb, ns, d_rows + row * (j - R.block_begin),
+                                    h->d_counter, h->stream, mode_tree(mode) ? 0 : s.waves, d_lstats,
                                     launches == 0 ? 1 : 0));   // (the tree kernels keep no wave records)
         h->counter_zero = true;
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-        if (walk_values)
-            HIP_TRY(hipMemcpyAsync(walk_values + walks_done * ns, h->d_val, sizeof(float) * count * ns,
+
+        // copy out the per-walk results, and wait
+        if (out.walk_values)
+            HIP_TRY(hipMemcpyAsync(out.walk_values + walks_done * ns, h->d_val, sizeof(float) * count * ns,
                                    hipMemcpyDeviceToHost, h->stream));
-        if (walk_steps)
-            HIP_TRY(hipMemcpyAsync(walk_steps + walks_done, h->d_steps, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, h->stream));
-        if (records)
-            HIP_TRY(hipMemcpyAsync(records + walks_done * rec_stride * kRecFloats, d_rec, (size_t)count * rec_walk_bytes,
+        if (out.walk_steps)
+            HIP_TRY(hipMemcpyAsync(out.walk_steps + walks_done, h->d_steps, sizeof(uint32_t) * count,
                                    hipMemcpyDeviceToHost, h->stream));
-        const bool last = j2 >= block_end;
-        if (last) {   // the block sums ride the same wait
-            HIP_TRY(hipMemcpyAsync(pin_bstats, h->d_bstats, sizeof(double) * (kLstatsWords + row * nblk),
+        if (out.records)
+            HIP_TRY(hipMemcpyAsync(out.records + walks_done * rec_stride * kRecFloats, d_rec, (size_t)count * rec_walk_bytes,
+                                   hipMemcpyDeviceToHost, h->stream));
+        if (b.j2 >= R.block_end) {   // the last batch: the block sums ride the same wait
+            HIP_TRY(hipMemcpyAsync(st.bstats, h->d_bstats, sizeof(double) * (kLstatsWords + row * R.nblk),
                                    hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipEventRecord(h->ev[5], h->stream));
             HIP_TRY(hipEventSynchronize(h->ev[5]));
@@ -1424,52 +1473,30 @@ int solve_impl(wost_handle* h, const float* points, int64_t n_points, int64_t W,
         red_ms += t1;
         ++launches;
         walks_done += count;
-        j = j2;
     }
-    if (O.tree_iter_stats && a.pool != nullptr) {   // study builds: the tree queries' loop counters
-        const int64_t nwg = (int64_t)blocks_per_cu * h->num_cus;
-        std::vector<uint32_t> pw((size_t)(a.pool_wg_words * nwg));
-        HIP_TRY(hipMemcpy(pw.data(), a.pool, sizeof(uint32_t) * pw.size(), hipMemcpyDeviceToHost));
-        const int64_t off = a.pool_wg_words - 16;
-        double c[16] = {};
-        for (int64_t g = 0; g < nwg; ++g)
-            for (int i = 0; i < 16; ++i) c[i] += pw[(size_t)(g * a.pool_wg_words + off + i)];
-        std::fprintf(stderr, "tree_iter_stats:");
-        for (int i = 0; i < 16; ++i) std::fprintf(stderr, " %.0f", c[i]);
-        std::fprintf(stderr, "\n");
-    }
-    const double* bs = pin_bstats + kLstatsWords;   // (copied and waited for with the last batch)
-    {   // the launch statistics (wost_kernels.hip reduce_wave_stats), wall-clock ticks
-        unsigned long long ls[kLstatsWords];
-        std::memcpy(ls, pin_bstats, sizeof(ls));
-        const double ms_per_tick = 1.0 / h->tick_khz;
-        h->timing.max_walk_steps = (uint32_t)std::min<unsigned long long>(ls[3], 0xFFFFFFFFull);
-        h->timing.span_ms = ls[2] > ls[0] ? (double)(ls[2] - ls[0]) * ms_per_tick : 0.0;
-        h->timing.tail_ms = ls[2] > ls[1] ? (double)(ls[2] - ls[1]) * ms_per_tick : 0.0;
-        h->timing.last_wave_ms = (double)ls[5] * ms_per_tick;
-        h->timing.last_wave_iters = (uint32_t)ls[4];
-        h->timing.max_wave_iters = (uint32_t)ls[6];
-    }
+    if ((rc = dump_tree_iter_stats(h, a, kc.blocks_per_cu)) != WOST_OK) return rc;
+    read_launch_stats(h, st.bstats);
     float tt = 0.f;
     HIP_TRY(hipEventElapsedTime(&tt, h->ev[4], h->ev[5]));
 
+    const double* bs = st.bstats + kLstatsWords;   // (copied and waited for with the last batch)
     uint64_t steps_sum = 0;
-    for (int64_t b = 0; b < nblk; ++b) {
-        steps_sum += (uint64_t)bs[row * b + row - 1];
-        if (point_stats) {
-            const int64_t p = (block_begin + b) / (range ? nbr : nbpp);
-            for (int c = 0; c < row; ++c) point_stats[row * p + c] += bs[row * b + c];
+    for (int64_t k = 0; k < R.nblk; ++k) {
+        steps_sum += (uint64_t)bs[row * k + row - 1];
+        if (out.point_stats) {
+            const int64_t p = R.point_of(R.block_begin + k);
+            for (int c = 0; c < row; ++c) out.point_stats[row * p + c] += bs[row * k + c];
         }
     }
-    if (block_stats) std::memcpy(block_stats, bs, sizeof(double) * row * nblk);
+    if (out.block_stats) std::memcpy(out.block_stats, bs, sizeof(double) * row * R.nblk);
     h->timing.walk_kernel_ms = walk_ms;
     h->timing.reduce_kernel_ms = red_ms;
     h->timing.total_ms = tt;
     h->timing.n_launches = launches;
     h->timing.total_steps = steps_sum;
-    h->timing.total_walks = (uint64_t)walks_total;
-    h->timing.jit_ms = jit_ms;
-    h->timing.jit = jfn ? 1 : 0;
+    h->timing.total_walks = (uint64_t)R.walks_total;
+    h->timing.jit_ms = kc.jit_ms;
+    h->timing.jit = kc.jfn ? 1 : 0;
     h->timing.tree = mode_tree(mode) ? 1 : 0;
     return WOST_OK;
 }
@@ -1500,6 +1527,69 @@ void add_timing(wost_timing& acc, const wost_timing& t) {
     acc.precompiled_walks += t.precompiled_walks;
 }
 
+// A solve of walks [w_begin, w_begin + Wr) of every point that takes several solves of
+// block-aligned sub-ranges (wost_solve_range beyond one launch per point, solve_race): each
+// piece's block rows, values and steps are scattered into the whole range's layout, so the
+// block sums, their order and every output are those of one solve.
+struct Stitch {
+    SolveRequest rq;       // the whole solve (its ranges set per piece)
+    SolveOutputs out;
+    int ns = 1;            // values per walk
+    int64_t w_begin = 0, Wr = 0, nbr = 0;
+    std::vector<double> all, part;   // block rows of the range / of a piece
+    std::vector<float> pv;
+    std::vector<uint32_t> ps;
+    wost_timing acc{};
+    double solve_ms = 0.0;   // host time of the last piece's solve
+
+    Stitch(const SolveRequest& whole, const SolveOutputs& o, int ns_, int64_t w0, int64_t w1)
+        : rq(whole), out(o), ns(ns_), w_begin(w0), Wr(w1 - w0), nbr((w1 - w0 + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS),
+          all((size_t)whole.n_points * nbr * (2 * ns_ + 1)) {}
+};
+
+// Solves walks [c0, c1) of every point into the stitched solve's outputs and timing.
+int solve_piece(wost_handle* h, Stitch& s, int64_t c0, int64_t c1) {
+    const int row = 2 * s.ns + 1;
+    const int64_t n_points = s.rq.n_points;
+    const int64_t wc = c1 - c0, nbc = (wc + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
+    const int64_t woff = c0 - s.w_begin, boff = woff / WOST_BLOCK_WALKS;
+    s.part.resize((size_t)n_points * nbc * row);
+    if (s.out.walk_values) s.pv.resize((size_t)n_points * wc * s.ns);
+    if (s.out.walk_steps) s.ps.resize((size_t)n_points * wc);
+    // (the whole of [0, W) is an ordinary solve of every block: solve_impl takes it as no range)
+    s.rq.walk_begin = c0;
+    s.rq.walk_end = c1;
+    SolveOutputs piece;
+    piece.block_stats = s.part.data();
+    piece.walk_values = s.out.walk_values ? s.pv.data() : nullptr;
+    piece.walk_steps = s.out.walk_steps ? s.ps.data() : nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = solve_impl(h, s.rq, piece);
+    s.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != WOST_OK) return rc;
+    for (int64_t p = 0; p < n_points; ++p) {
+        std::memcpy(&s.all[((size_t)p * s.nbr + boff) * row], &s.part[(size_t)p * nbc * row], sizeof(double) * nbc * row);
+        if (s.out.walk_values)
+            std::memcpy(s.out.walk_values + ((size_t)p * s.Wr + woff) * s.ns, &s.pv[(size_t)p * wc * s.ns],
+                        sizeof(float) * wc * s.ns);
+        if (s.out.walk_steps)
+            std::memcpy(s.out.walk_steps + (size_t)p * s.Wr + woff, &s.ps[(size_t)p * wc], sizeof(uint32_t) * wc);
+    }
+    add_timing(s.acc, h->timing);
+    return WOST_OK;
+}
+
+// The stitched solve's block rows and point sums (in the range's block order) to the caller.
+void stitched_stats(const Stitch& s) {
+    const int row = 2 * s.ns + 1;
+    if (s.out.block_stats) std::memcpy(s.out.block_stats, s.all.data(), sizeof(double) * s.all.size());
+    if (!s.out.point_stats) return;
+    std::fill(s.out.point_stats, s.out.point_stats + (size_t)row * s.rq.n_points, 0.0);
+    for (int64_t p = 0; p < s.rq.n_points; ++p)
+        for (int64_t k = 0; k < s.nbr; ++k)
+            for (int c = 0; c < row; ++c) s.out.point_stats[(size_t)row * p + c] += s.all[((size_t)p * s.nbr + k) * row + c];
+}
+
 // A whole single-source solve whose field-specialised kernel is in no cache (option
 // jit_race; the reference calls solve() once per script): its compile starts in a helper
 // process, and meanwhile the precompiled kernel -- the same bits walk for walk
@@ -1510,18 +1600,14 @@ void add_timing(wost_timing& acc, const wost_timing& t) {
 // A solve that finds the compile already running waits for it instead (jit_get_kernel).
 constexpr double kCompileExpectMs = 300.0;   // a specialised kernel's compile (MI355X box: 180-600 ms)
 
-int solve_race(wost_handle* h, const float* points, int64_t n_points, int64_t W, int32_t max_steps, float eps,
-               uint64_t seed, double* block_stats, double* point_stats, float* walk_values, uint32_t* walk_steps) {
-    const int64_t nb = wost_num_blocks(n_points, W);
-    auto plain = [&]() {
-        return solve_impl(h, points, n_points, W, 0, nb, max_steps, eps, seed, block_stats, point_stats, walk_values,
-                          walk_steps, nullptr);
-    };
-    if (!points) return plain();
+int solve_race(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) {
+    const float* points = rq.points;
+    const int64_t n_points = rq.n_points, W = rq.W;
+    if (!points) return solve_impl(h, rq, out);
     for (int64_t i = 0; i < 2 * n_points; ++i)
-        if (!std::isfinite(points[i])) return plain();   // (its error message)
+        if (!std::isfinite(points[i])) return solve_impl(h, rq, out);   // (its error message)
     const int mode = walk_mode(h);
-    if (mode_delta(mode) && !h->fields[SLOT_F].present) return plain();
+    if (mode_delta(mode) && !h->fields[SLOT_F].present) return solve_impl(h, rq, out);
     HIP_TRY(hipSetDevice(h->device));
     int rc;
     if ((rc = upload_program(h)) != WOST_OK) return rc;
@@ -1529,11 +1615,9 @@ int solve_race(wost_handle* h, const float* points, int64_t n_points, int64_t W,
     KernelShape ks;
     if ((rc = first_kernel_shape(h, mode, n_points, &ks)) != WOST_OK) return rc;
     JitTicket ticket;
-    const int stage = ks.tree_lds > 0 ? (ks.tree_verts > 0 ? 2 : 1) : 0;
-    if (jit_kernel_try(h, mode, ks.block, ks.gpoly, stage, &ticket) != JitTry::kStarted) return plain();
+    if (jit_kernel_try(h, mode, ks.block, ks.gpoly, ks.stage(), &ticket) != JitTry::kStarted)
+        return solve_impl(h, rq, out);
 
-    const int row = 3;
-    const int64_t nbpp = (W + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
     const int64_t max_piece = kMaxBatchWalks / WOST_BLOCK_WALKS * WOST_BLOCK_WALKS;   // walks of a point per launch
     auto blocks_up = [](double walks) {
         const double b = std::ceil(std::max(walks, 1.0) / WOST_BLOCK_WALKS);
@@ -1541,46 +1625,28 @@ int solve_race(wost_handle* h, const float* points, int64_t n_points, int64_t W,
     };
     int64_t piece = std::min(max_piece, blocks_up((double)(1 << 19) / (double)n_points));
     const auto race_t0 = std::chrono::steady_clock::now();
-    std::vector<double> all((size_t)n_points * nbpp * row), part;
-    std::vector<float> pv;
-    std::vector<uint32_t> ps;
-    wost_timing acc{};
+    Stitch st(rq, out, 1, 0, W);
     bool jit_now = false;
     const bool saved = h->jit_enabled;
     for (int64_t w0 = 0; w0 < W;) {
         if (!jit_now && ticket.done()) jit_now = true;
         const int64_t w1 = std::min(W, w0 + (jit_now ? max_piece : piece));
-        const int64_t wc = w1 - w0, nbc = (wc + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
-        part.resize((size_t)n_points * nbc * row);
-        if (walk_values) pv.resize((size_t)n_points * wc);
-        if (walk_steps) ps.resize((size_t)n_points * wc);
+        const int64_t wc = w1 - w0;
         h->jit_enabled = jit_now;
-        const auto t0 = std::chrono::steady_clock::now();
-        // (the whole range is an ordinary solve: solve_impl takes [0, W) as no range)
-        const bool whole = w0 == 0 && w1 == W;
-        rc = solve_impl(h, points, n_points, W, 0, whole ? nb : 0, max_steps, eps, seed, part.data(), nullptr,
-                        walk_values ? pv.data() : nullptr, walk_steps ? ps.data() : nullptr, nullptr, false, w0,
-                        whole ? -1 : w1);
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        rc = solve_piece(h, st, w0, w1);
         h->jit_enabled = saved;
         if (rc == WOST_ERR_UNSUPPORTED && !jit_now) {   // (a shape only the specialised kernel runs)
             jit_now = true;
             continue;
         }
         if (rc != WOST_OK) return rc;
-        const int64_t boff = w0 / WOST_BLOCK_WALKS;
-        for (int64_t p = 0; p < n_points; ++p) {
-            std::memcpy(&all[((size_t)p * nbpp + boff) * row], &part[(size_t)p * nbc * row], sizeof(double) * nbc * row);
-            if (walk_values) std::memcpy(walk_values + (size_t)p * W + w0, &pv[(size_t)p * wc], sizeof(float) * wc);
-            if (walk_steps) std::memcpy(walk_steps + (size_t)p * W + w0, &ps[(size_t)p * wc], sizeof(uint32_t) * wc);
-        }
         if (!jit_now) {
-            h->timing.precompiled_walks = (uint64_t)(n_points * wc);
+            st.acc.precompiled_walks += (uint64_t)(n_points * wc);
             // the next range, from this one's rate: all the rest when the precompiled kernel
             // finishes it before the compile is likely done (every range ends in a tail of
             // the longest walks: one launch, not many); else about half the compile's
             // expected remaining time, at least 16 ms of work, at most 8x this range
-            const double rate = (double)wc / std::max(ms, 0.05);   // walks per point per ms
+            const double rate = (double)wc / std::max(st.solve_ms, 0.05);   // walks per point per ms
             const double since = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() -
                                                                             race_t0).count();
             const double compile_left = std::max(0.0, kCompileExpectMs - since);
@@ -1591,20 +1657,14 @@ int solve_race(wost_handle* h, const float* points, int64_t n_points, int64_t W,
                 piece = std::min(max_piece, std::max(piece, std::min(8 * piece, blocks_up(rate * target))));
             }
         }
-        add_timing(acc, h->timing);
         w0 = w1;
     }
-    if (block_stats) std::memcpy(block_stats, all.data(), sizeof(double) * all.size());
-    if (point_stats) {
-        std::fill(point_stats, point_stats + (size_t)row * n_points, 0.0);
-        for (int64_t p = 0; p < n_points; ++p)
-            for (int64_t b = 0; b < nbpp; ++b)
-                for (int c = 0; c < row; ++c) point_stats[(size_t)row * p + c] += all[((size_t)p * nbpp + b) * row + c];
-    }
-    acc.jit = jit_now ? 1 : 0;
-    h->timing = acc;
+    stitched_stats(st);
+    st.acc.jit = jit_now ? 1 : 0;
+    h->timing = st.acc;
     return WOST_OK;
 }
+
 
 // The handle's fields with sources[0..n) in the source slots (wost_set_sources' conversion).
 int fields_with_sources(const wost_handle* h, const wost_field* const* sources, int32_t n, HostField* out) {
@@ -1639,66 +1699,45 @@ extern "C" {
 int wost_solve(wost_handle* h, const float* points, int64_t n_points, int64_t W,
                int64_t block_begin, int64_t block_end, int32_t max_steps, float eps, uint64_t seed,
                double* block_stats, double* point_stats, float* walk_values, uint32_t* walk_steps) {
+    SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
+    SolveOutputs out;
+    out.block_stats = block_stats; out.point_stats = point_stats;
+    out.walk_values = walk_values; out.walk_steps = walk_steps;
     // a whole single-source solve may start on the precompiled kernel while its specialised
     // one compiles (solve_race)
     if (h && h->jit_enabled && h->opt.jit_race && h->channels() == 1 && n_points > 0 && W > 0 && block_begin == 0 &&
-        block_end == wost_num_blocks(n_points, W) && max_steps >= 0 && eps == eps)
-        return solve_race(h, points, n_points, W, max_steps, eps, seed, block_stats, point_stats, walk_values,
-                          walk_steps);
-    return solve_impl(h, points, n_points, W, block_begin, block_end, max_steps, eps, seed, block_stats,
-                      point_stats, walk_values, walk_steps, nullptr);
+        block_end == rq.block_end && max_steps >= 0 && eps == eps)
+        return solve_race(h, rq, out);
+    rq.block_begin = block_begin;
+    rq.block_end = block_end;
+    return solve_impl(h, rq, out);
 }
 
 int wost_solve_range(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t walk_begin,
                      int64_t walk_end, int32_t max_steps, float eps, uint64_t seed, double* block_stats,
                      double* point_stats, float* walk_values, uint32_t* walk_steps) {
     if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
-    if (walk_begin == 0 && walk_end == W) {   // the whole range: an ordinary solve
-        const int64_t nb = wost_num_blocks(n_points, W);
-        return solve_impl(h, points, n_points, W, 0, nb, max_steps, eps, seed, block_stats, point_stats,
-                          walk_values, walk_steps, nullptr, true);
-    }
+    SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
+    rq.multi = true;
+    SolveOutputs out;
+    out.block_stats = block_stats; out.point_stats = point_stats;
+    out.walk_values = walk_values; out.walk_steps = walk_steps;
+    if (walk_begin == 0 && walk_end == W) return solve_impl(h, rq, out);   // the whole range: an ordinary solve
     const int ns = h->channels();
     const int64_t chunk = (kMaxBatchWalks / ns) / WOST_BLOCK_WALKS * WOST_BLOCK_WALKS;   // walks of a point per launch
-    if (walk_end - walk_begin <= chunk || walk_begin < 0 || walk_end <= walk_begin || n_points <= 0)
-        return solve_impl(h, points, n_points, W, 0, 0, max_steps, eps, seed, block_stats, point_stats, walk_values,
-                          walk_steps, nullptr, true, walk_begin, walk_end);
+    if (walk_end - walk_begin <= chunk || walk_begin < 0 || walk_end <= walk_begin || n_points <= 0) {
+        rq.block_end = 0;   // (a range names its walks only)
+        rq.walk_begin = walk_begin;
+        rq.walk_end = walk_end;
+        return solve_impl(h, rq, out);
+    }
     // a range longer than one launch holds per point: block-aligned sub-ranges, one solve
     // each, scattered into the range's layout; point sums in the range's block order
-    const int row = 2 * ns + 1;
-    const int64_t Wr = walk_end - walk_begin;
-    const int64_t nbr = (Wr + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
-    std::vector<double> all((size_t)n_points * nbr * row);
-    std::vector<double> part;
-    std::vector<float> pv;
-    std::vector<uint32_t> ps;
-    wost_timing acc{};
-    for (int64_t c0 = walk_begin; c0 < walk_end; c0 += chunk) {
-        const int64_t c1 = std::min(walk_end, c0 + chunk);
-        const int64_t wc = c1 - c0, nbc = (wc + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
-        const int64_t boff = (c0 - walk_begin) / WOST_BLOCK_WALKS, woff = c0 - walk_begin;
-        part.resize((size_t)n_points * nbc * row);
-        if (walk_values) pv.resize((size_t)n_points * wc * ns);
-        if (walk_steps) ps.resize((size_t)n_points * wc);
-        int rc = solve_impl(h, points, n_points, W, 0, 0, max_steps, eps, seed, part.data(), nullptr,
-                            walk_values ? pv.data() : nullptr, walk_steps ? ps.data() : nullptr, nullptr, true, c0, c1);
-        if (rc != WOST_OK) return rc;
-        for (int64_t p = 0; p < n_points; ++p) {
-            std::memcpy(&all[((size_t)p * nbr + boff) * row], &part[(size_t)p * nbc * row], sizeof(double) * nbc * row);
-            if (walk_values)
-                std::memcpy(walk_values + ((size_t)p * Wr + woff) * ns, &pv[(size_t)p * wc * ns], sizeof(float) * wc * ns);
-            if (walk_steps) std::memcpy(walk_steps + (size_t)p * Wr + woff, &ps[(size_t)p * wc], sizeof(uint32_t) * wc);
-        }
-        add_timing(acc, h->timing);
-    }
-    if (block_stats) std::memcpy(block_stats, all.data(), sizeof(double) * all.size());
-    if (point_stats) {
-        std::fill(point_stats, point_stats + (size_t)row * n_points, 0.0);
-        for (int64_t p = 0; p < n_points; ++p)
-            for (int64_t b = 0; b < nbr; ++b)
-                for (int c = 0; c < row; ++c) point_stats[(size_t)row * p + c] += all[((size_t)p * nbr + b) * row + c];
-    }
-    h->timing = acc;
+    Stitch st(rq, out, ns, walk_begin, walk_end);
+    for (int64_t c0 = walk_begin; c0 < walk_end; c0 += chunk)
+        if (int rc = solve_piece(h, st, c0, std::min(walk_end, c0 + chunk))) return rc;
+    stitched_stats(st);
+    h->timing = st.acc;
     return WOST_OK;
 }
 
@@ -1706,17 +1745,27 @@ int wost_solve_history(wost_handle* h, const float* points, int64_t n_points, in
                        float eps, uint64_t seed, double* point_stats, float* walk_values, uint32_t* walk_steps,
                        float* records) {
     if (!records) return fail(WOST_ERR_INVALID_ARG, "NULL records");
-    const int64_t nb = wost_num_blocks(n_points, W);
-    return solve_impl(h, points, n_points, W, 0, nb, max_steps, eps, seed, nullptr, point_stats, walk_values,
-                      walk_steps, records);
+    SolveOutputs out;
+    out.point_stats = point_stats;
+    out.walk_values = walk_values;
+    out.walk_steps = walk_steps;
+    out.records = records;
+    return solve_impl(h, whole_request(points, n_points, W, max_steps, eps, seed), out);
 }
 
 int wost_solve_multi(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t block_begin,
                      int64_t block_end, int32_t max_steps, float eps, uint64_t seed, double* block_stats,
                      double* point_stats, float* walk_values, uint32_t* walk_steps) {
-    return solve_impl(h, points, n_points, W, block_begin, block_end, max_steps, eps, seed, block_stats, point_stats,
-                      walk_values, walk_steps, nullptr, true);
+    SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
+    rq.multi = true;
+    rq.block_begin = block_begin;
+    rq.block_end = block_end;
+    SolveOutputs out;
+    out.block_stats = block_stats; out.point_stats = point_stats;
+    out.walk_values = walk_values; out.walk_steps = walk_steps;
+    return solve_impl(h, rq, out);
 }
+
 
 int wost_set_sources(wost_handle* h, const wost_field* const* sources, int32_t n) {
     if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
@@ -1754,9 +1803,8 @@ int wost_prepare_sources(wost_handle* h, const wost_field* const* sources, int32
     }
     KernelShape ks;
     if ((rc = first_kernel_shape(h, mode, n_points, &ks)) != WOST_OK) return rc;
-    const int stage = ks.tree_lds > 0 ? (ks.tree_verts > 0 ? 2 : 1) : 0;
     std::string src, err;
-    if ((rc = jit_source(h, prog, mode, false, n, ks.block, ks.gpoly, stage, &src)) != WOST_OK) return rc;
+    if ((rc = jit_source(h, prog, mode, false, n, ks.block, ks.gpoly, ks.stage(), &src)) != WOST_OK) return rc;
     hipFunction_t fn = nullptr;
     if (!jit_get_kernel(h->opt, h->device, src, &fn, &err, nullptr, nullptr))
         return fail(WOST_ERR_UNSUPPORTED, "field-specialised kernel unavailable: %s", err.c_str());

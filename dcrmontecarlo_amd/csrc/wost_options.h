@@ -58,7 +58,7 @@ struct Options {
                                     // concurrent handles' compiles overlap), 0: in this process
     int jit_race = 1;               // a whole solve whose specialised kernel is in no cache runs on the
                                     // precompiled kernel while it compiles (wost_api.hip solve_race)
-    // work queue (wost_api.hip solve_impl; -1 / 0: the call's own shape)
+    // work queue (wost_launch.cpp launch_shape; -1 / 0: the call's own shape)
     int chunk0 = -1;
     int chunk_min = -1;
     int chunk_max = -1;

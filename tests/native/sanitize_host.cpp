@@ -1,6 +1,6 @@
 // TEST HARNESS -- AddressSanitizer / UndefinedBehaviorSanitizer run of libwost's
 // host-side C++ (segment-tree builder wost_tree.cpp, sampler / Green's-norm tables
-// wost_tables.cpp) and of the C oracle (oracle/wost_oracle.c), built by
+// wost_tables.cpp, the launch plan wost_launch.cpp) and of the C oracle (oracle/wost_oracle.c), built by
 // tests/test_sanitizers.py with -fsanitize=address,undefined -fno-sanitize-recover.
 // Exercises ordinary, degenerate and extreme inputs; exits non-zero on a failed
 // check (a sanitizer finding aborts the process by itself).
@@ -10,6 +10,7 @@
 #include <random>
 #include <vector>
 
+#include "../../dcrmontecarlo_amd/csrc/wost_launch.h"
 #include "../../dcrmontecarlo_amd/csrc/wost_tables.h"
 #include "../../dcrmontecarlo_amd/csrc/wost_tree.h"
 #include "../../oracle/wost_oracle.h"
@@ -74,6 +75,41 @@ int main() {
         }
     for (double x : {0.0, 1e-8, 1.0, 30.0, 700.0, 1e6}) CHECK(!std::isnan(wost::i0e_host(x)));
     for (double x : {1e-8, 1.0, 3.0, 50.0}) CHECK(std::isfinite(wost::k0_host(x)));
+    // --- the launch plan (wost_launch.cpp): batches of a few blocks, the extremes of a shape
+    for (int64_t W : {int64_t(1), int64_t(5000), int64_t(1) << 31, (int64_t(1) << 53) / 5})
+        for (int range = 0; range < 2; ++range) {
+            const int64_t nbpp = (W + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
+            if (range && W < 2 * WOST_BLOCK_WALKS) continue;
+            wost::SolveRanges r;
+            char msg[64];   // (shorter than the messages: they are cut, not overrun)
+            CHECK(wost::plan_ranges(5, W, 0, 5 * nbpp + 1, 0, -1, &r, msg, sizeof(msg)) != 0);
+            CHECK(wost::plan_ranges(5, W, 0, 0, 7, W, &r, msg, sizeof(msg)) != 0);
+            const int rc = range ? wost::plan_ranges(5, W, 0, 0, WOST_BLOCK_WALKS, 2 * WOST_BLOCK_WALKS, &r, msg, sizeof(msg))
+                                 : wost::plan_ranges(5, W, 5 * nbpp - 7 > 0 ? 5 * nbpp - 7 : 0, 5 * nbpp, 0, -1, &r, msg,
+                                                     sizeof(msg));
+            CHECK(rc == 0);
+            wost::Batch b;
+            int64_t walks = 0;
+            for (int64_t j = r.block_begin; j < r.block_end; j = b.j2) {
+                if (!wost::next_batch(r, j, 3 * WOST_BLOCK_WALKS, &b)) { CHECK(false); break; }
+                walks += b.count;
+            }
+            CHECK(walks == r.walks_total);
+        }
+    for (int64_t count : {int64_t(1), int64_t(640000), int64_t(1) << 26})
+        for (int block : {64, 256, 1024}) {
+            wost::Options o;
+            wost::LaunchIn in;
+            in.short_walks = block == 256;
+            in.tree = block == 1024;
+            in.count = count;
+            in.block = block;
+            in.blocks_per_cu = 8;
+            in.num_cus = 256;
+            in.opt = &o;
+            const wost::LaunchShape s = wost::launch_shape(in);
+            CHECK(s.grid >= 1 && s.waves == (int64_t)s.grid * (block / 64) && s.chunk >= 1 && s.queue_base == s.waves * s.chunk0);
+        }
     // --- the oracle: queries on degenerate geometry, and small solves of each mode
     for (int kind = 0; kind < 4; ++kind) {
         const std::vector<float> xy = polyline(rng, 33, kind);

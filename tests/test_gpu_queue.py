@@ -1,5 +1,5 @@
-"""The walk kernels' work queue and launch shape (wost_walk.h refill, wost_api.hip
-solve_impl): a walk's result depends only on its id, so every queue shape gives the
+"""The walk kernels' work queue and launch shape (wost_walk.h refill, wost_launch.cpp
+launch_shape): a walk's result depends only on its id, so every queue shape gives the
 same bits.
 
 Round 6: the launch shape is a function of the call alone (never of an earlier solve on
@@ -100,6 +100,72 @@ def test_static_chunks_cover_every_walk(gpu_available):
         np.testing.assert_array_equal(got[1], ref[1])
         np.testing.assert_array_equal(got[0], ref[0])
         assert (got[1] > 0).all()
+
+
+def _walks_call(name, n, W):
+    def run():
+        sc = _scenario(name)
+        s = sc.solver(device=0)
+        s.set_option("jit_race", 0)
+        _walks(s, np.resize(sc.points, (n, 2)).astype(np.float32), W, sc, seed=7)
+        return s
+    return run
+
+
+def _range_call():
+    sc = _scenario("poisson_square")
+    s = sc.solver(device=0)
+    s.set_option("jit_race", 0)
+    s.solve_range(np.resize(sc.points, (3, 2)).astype(np.float32), 9000, 4096, 9000, maxSteps=sc.max_steps,
+                  eps=sc.eps, seed=7)
+    return s
+
+
+def _wavenumber_call():
+    from dcrmontecarlo_amd.wavenumber import sigma_bar_for
+
+    sc = _scenario("variable_coefficients")
+    k = np.sqrt(np.array([0.0, 0.25, 1.0, 2.0]))
+    s = sc.solver(device=0, sigma_bar=sigma_bar_for(sc, float(k.max())))
+    s.set_option("jit_race", 0)
+    s.solve_wavenumbers(np.resize(sc.points, (3, 2)).astype(np.float32), k, nWalks=2000, maxSteps=sc.max_steps,
+                        eps=sc.eps, seed=7)
+    return s
+
+
+# the calls whose launch shapes tests/golden/launch_shapes_parent.json records
+SHAPE_CALLS = {
+    "poisson_square-3x100": _walks_call("poisson_square", 3, 100),
+    "poisson_square-64x3000": _walks_call("poisson_square", 64, 3000),
+    "poisson_square-64x4000": _walks_call("poisson_square", 64, 4000),
+    "dcr_dipole-5x300": _walks_call("dcr_dipole", 5, 300),
+    "dcr_dipole-48x2000": _walks_call("dcr_dipole", 48, 2000),
+    "wenner_topography-8x200": _walks_call("wenner_topography", 8, 200),
+    "laplace_square-2x1": _walks_call("laplace_square", 2, 1),
+    "laplace_square-2x7": _walks_call("laplace_square", 2, 7),
+    "laplace_square-2x64": _walks_call("laplace_square", 2, 64),
+    "laplace_square-2x65": _walks_call("laplace_square", 2, 65),
+    "solve_range-3x[4096,9000)": _range_call,
+    "solve_wavenumbers-4ch-3x2000": _wavenumber_call,
+}
+
+
+def recorded_shape(s) -> dict:
+    return {k: int(s.last_timing[k]) for k in SHAPE + ("n_launches",)}
+
+
+@pytest.mark.parametrize("call", sorted(SHAPE_CALLS))
+def test_launch_shape_is_the_recorded_one(gpu_available, call):
+    """The launch shape (csrc/wost_launch.cpp launch_shape) and the number of launches of
+    each call equal those recorded from the library before solve_impl was split into a
+    launch plan and steps (tests/golden/launch_shapes_parent.json)."""
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "launch_shapes_parent.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(SHAPE_CALLS)
+    assert recorded_shape(SHAPE_CALLS[call]()) == want[call]
 
 
 @pytest.mark.parametrize("name", ["poisson_square", "dcr_dipole"])

@@ -1,5 +1,5 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer over libwost's host-side C++ (the
-segment-tree builder and the sampler / Green's-norm tables) and the C oracle
+segment-tree builder, the sampler / Green's-norm tables, the launch plan) and the C oracle
 (sanitizers on host code; GPU sanitizers are not available). The
 harness tests/native/sanitize_host.cpp drives ordinary, degenerate and extreme
 inputs; any sanitizer finding aborts it (-fno-sanitize-recover)."""
@@ -23,7 +23,8 @@ def test_host_code_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "sanitize_host")
     subprocess.run(["g++", "-std=c++17", "-fopenmp", *SAN, "-I" + os.path.join(REPO, "include"),
                     os.path.join(HERE, "native", "sanitize_host.cpp"), os.path.join(CSRC, "wost_tree.cpp"),
-                    os.path.join(CSRC, "wost_tables.cpp"), oracle_o, "-o", exe, "-lm"], check=True)
+                    os.path.join(CSRC, "wost_tables.cpp"), os.path.join(CSRC, "wost_launch.cpp"),
+                    oracle_o, "-o", exe, "-lm"], check=True)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1",
                OMP_NUM_THREADS="2")
     r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
