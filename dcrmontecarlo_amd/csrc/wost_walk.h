@@ -104,6 +104,53 @@ struct WalkArgs {
     float k2[WOST_MAX_SOURCES];
 };
 
+// The refill's id arithmetic: local walk `lid` of the launch `A` -> its global walk id `wid`
+// and its point index `pid` (uint64_t lvalues). Integer quotients without a 64-bit division:
+// a double estimate (exact operands below 2^53) and one correction. Three paths, chosen by
+// the launch (wost_launch.h next_batch): walk-range batches (local index < 2^26, one launch:
+// a 32-bit quotient), 32-bit offsets (small32), and 64 bits.
+// A statement macro and not a function: walk_body expands it, and walk_of_local below wraps
+// the same text for the host check (tests/native/walk_ids_check.cpp). As a forced-inline
+// function called from walk_body it changed the register allocation of the segment-tree
+// kernels; expanded in place their code is instruction for instruction what it was.
+// WOST_WALK_ID_CORRECTED(path, dir): the host check's counter of the corrections that fire
+// (path 0 range, 1 small32, 2 64-bit; dir -1 / +1); nothing in the kernels.
+#ifndef WOST_WALK_ID_CORRECTED
+#define WOST_WALK_ID_CORRECTED(path, dir)
+#endif
+#define WOST_WALK_OF_LOCAL(A, lid, wid, pid) \
+    if (A.range_walks > 0) { \
+        const uint32_t l32 = (uint32_t)lid, rw = (uint32_t)A.range_walks; \
+        uint32_t q = (uint32_t)((double)l32 * A.inv_range_walks); \
+        int32_t rem = (int32_t)(l32 - q * rw); \
+        if (rem < 0) { --q; rem += (int32_t)rw; WOST_WALK_ID_CORRECTED(0, -1) } \
+        else if (rem >= (int32_t)rw) { ++q; rem -= (int32_t)rw; WOST_WALK_ID_CORRECTED(0, +1) } \
+        pid = (uint64_t)A.range_point0 + q; \
+        wid = pid * (uint64_t)A.walks_per_point + (uint64_t)A.range_offset + (uint64_t)rem; \
+    } else if (A.small32) { \
+        const uint32_t local = A.base_off + (uint32_t)lid, w32 = (uint32_t)A.walks_per_point; \
+        uint32_t q = (uint32_t)((double)local * A.inv_walks_per_point); \
+        const int32_t rem = (int32_t)(local - q * w32); \
+        if (rem < 0) { --q; WOST_WALK_ID_CORRECTED(1, -1) } \
+        else if (rem >= (int32_t)w32) { ++q; WOST_WALK_ID_CORRECTED(1, +1) } \
+        pid = (uint64_t)A.base_pid + q; \
+        wid = (uint64_t)A.wid_begin + lid; \
+    } else { \
+        wid = (uint64_t)A.wid_begin + lid; \
+        pid = (uint64_t)((double)wid * A.inv_walks_per_point); \
+        const int64_t rem = (int64_t)(wid - pid * (uint64_t)A.walks_per_point); \
+        if (rem < 0) { --pid; WOST_WALK_ID_CORRECTED(2, -1) } \
+        else if (rem >= A.walks_per_point) { ++pid; WOST_WALK_ID_CORRECTED(2, +1) } \
+    }
+
+// WOST_WALK_OF_LOCAL as a function: the point index of local walk lid, its global id in *wid.
+WOST_HD uint64_t walk_of_local(const WalkArgs& A, uint64_t lid, uint64_t* wid) {
+    uint64_t pid, g;
+    WOST_WALK_OF_LOCAL(A, lid, g, pid)
+    *wid = g;
+    return pid;
+}
+
 // The walk launch's control words (WalkArgs::counter): [0] the work-queue head, [1] the
 // block reduce's finished-workgroup count, [2] its longest walk (kernels without wave
 // records), [3] unused; then per wave two uint4 of launch statistics: {start tick low, high,
@@ -1132,33 +1179,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             const uint32_t rank = (uint32_t)__popcll(need & lanes_below);
             if ((need & lanebit) && rank < take) {
                 lid = c_next + rank;
-                // integer quotients without a 64-bit division: a double estimate
-                // (exact operands below 2^53) and one correction
                 uint64_t pid;
-                if (A.range_walks > 0) {
-                    // local index < 2^26 (one launch): a 32-bit quotient
-                    const uint32_t l32 = (uint32_t)lid, rw = (uint32_t)A.range_walks;
-                    uint32_t q = (uint32_t)((double)l32 * A.inv_range_walks);
-                    int32_t rem = (int32_t)(l32 - q * rw);
-                    if (rem < 0) { --q; rem += (int32_t)rw; }
-                    else if (rem >= (int32_t)rw) { ++q; rem -= (int32_t)rw; }
-                    pid = (uint64_t)A.range_point0 + q;
-                    wid = pid * (uint64_t)A.walks_per_point + (uint64_t)A.range_offset + (uint64_t)rem;
-                } else if (A.small32) {
-                    const uint32_t local = A.base_off + (uint32_t)lid, w32 = (uint32_t)A.walks_per_point;
-                    uint32_t q = (uint32_t)((double)local * A.inv_walks_per_point);
-                    const int32_t rem = (int32_t)(local - q * w32);
-                    if (rem < 0) --q;
-                    else if (rem >= (int32_t)w32) ++q;
-                    pid = (uint64_t)A.base_pid + q;
-                    wid = (uint64_t)A.wid_begin + lid;
-                } else {
-                    wid = (uint64_t)A.wid_begin + lid;
-                    pid = (uint64_t)((double)wid * A.inv_walks_per_point);
-                    const int64_t rem = (int64_t)(wid - pid * (uint64_t)A.walks_per_point);
-                    if (rem < 0) --pid;
-                    else if (rem >= A.walks_per_point) ++pid;
-                }
+                WOST_WALK_OF_LOCAL(A, lid, wid, pid)
                 pw = philox_walk(wid, A.key0, A.key1);
                 if (WOST_PHILOX_AHEAD) rn_ahead = philox_draw(pw, 0u, A.key0, A.key1);
                 const float2 q = A.points[pid];

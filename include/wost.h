@@ -220,6 +220,9 @@ int64_t wost_num_blocks(int64_t n_points, int64_t walks_per_point);
  * [block_begin, block_end) (pass 0, wost_num_blocks(...) for a full solve).
  * Walk w of point p has global id p*walks_per_point + w; its random stream is
  * Philox4x32-10 keyed by seed, subsequence = global id, one draw per step.
+ * Block ranges of a solve of up to 2^53 walks (n_points * walks_per_point) are
+ * supported: a range is the full solve's blocks bit for bit, tested at walk ids
+ * above 2^32 (tests/test_gpu_walk_ids.py).
  *
  * Outputs (host memory, caller-owned; any may be NULL):
  *   block_stats [n_blocks_in_range][3] : sum, sum of squares, steps per block
