@@ -1309,6 +1309,33 @@ void read_launch_stats(wost_handle* h, const double* pin_bstats) {
     h->timing.max_wave_iters = (uint32_t)ls[6];
 }
 
+// Study builds (vote_stats): the wave votes' counters of the field-specialised kernel
+// (wost_device.h WOST_VOTE: per site the times it ran, the times a lane needed the slow
+// side, the lanes that needed it), a module-scope array the waves add to at their ends.
+constexpr int kVoteWords = 3 * 16;
+
+int vote_stats_begin(const wost_handle* h, hipFunction_t jfn, void** d_votes) {
+    *d_votes = nullptr;
+    if (!h->opt.vote_stats || !jfn) return WOST_OK;
+    size_t bytes = 0;
+    if (!jit_kernel_global(jfn, "wost_vote_words", d_votes, &bytes) || bytes != sizeof(uint64_t) * kVoteWords) {
+        *d_votes = nullptr;   // (a kernel from before the option was set)
+        return WOST_OK;
+    }
+    HIP_TRY(hipMemsetAsync(*d_votes, 0, bytes, h->stream));
+    return WOST_OK;
+}
+
+int dump_vote_stats(const void* d_votes) {   // (after the solve's last wait)
+    if (!d_votes) return WOST_OK;
+    uint64_t c[kVoteWords];
+    HIP_TRY(hipMemcpy(c, d_votes, sizeof(c), hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "vote_stats:");
+    for (int i = 0; i < kVoteWords; ++i) std::fprintf(stderr, " %llu", (unsigned long long)c[i]);
+    std::fprintf(stderr, "\n");
+    return WOST_OK;
+}
+
 // Study builds (tree_iter_stats): the tree queries' loop counters, summed over the workgroups.
 int dump_tree_iter_stats(const wost_handle* h, const WalkArgs& a, int blocks_per_cu) {
     if (!h->opt.tree_iter_stats || a.pool == nullptr) return WOST_OK;
@@ -1400,6 +1427,10 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
     shape_in.opt = &h->opt;
     shape_in.clock_is_100mhz = h->tick_khz == 100000.0;
 
+    // study builds (vote_stats): the specialised kernel's vote counters, zeroed before the launches
+    void* d_votes = nullptr;
+    if ((rc = vote_stats_begin(h, kc.jfn, &d_votes)) != WOST_OK) return rc;
+
     Batch& b = h->batch;
     HIP_TRY(hipEventRecord(h->ev[4], h->stream));
     int64_t walks_done = 0;
@@ -1475,6 +1506,7 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
         walks_done += count;
     }
     if ((rc = dump_tree_iter_stats(h, a, kc.blocks_per_cu)) != WOST_OK) return rc;
+    if ((rc = dump_vote_stats(d_votes)) != WOST_OK) return rc;
     read_launch_stats(h, st.bstats);
     float tt = 0.f;
     HIP_TRY(hipEventElapsedTime(&tt, h->ev[4], h->ev[5]));

@@ -290,6 +290,8 @@ std::string sat_call(const DFactor& f) {
     return o.str();
 }
 
+constexpr int kVoteStatsFlag = 1 << 30;   // jet_body's xflags: option vote_stats (above exp_flags' bits)
+
 // Same operation sequence as wost::field_jet. When every factor has a saturation
 // predicate and the coefficients are finite, a wave whose lanes are all saturated
 // returns {value, z, z, z} (wost_device.h, whole-field saturation): the value from
@@ -314,6 +316,7 @@ std::string jet_body(const DField& fd, const DTerm* terms, const DFactor* factor
             o << "        {\n"
               << "            bool centre = false;\n"
               << "            const bool sat = " << s.str() << ";\n"
+              << ((xflags & kVoteStatsFlag) ? "            WOST_VOTE(12, !sat);\n" : "")
               << "            if (WOST_SAT_ALL(sat)) {\n"
               << "                const float z = " << (radial ? "centre ? __builtin_nanf(\"\") : 0.0f" : "0.0f")
               << ";\n"
@@ -741,6 +744,7 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
     if (opt.tree_share_descent >= 0) o << "#define WOST_TREE_SHARE_DESCENT " << opt.tree_share_descent << "\n";
     if (opt.pool_min_push != 1) o << "#define WOST_POOL_MIN_PUSH " << opt.pool_min_push << "\n";
     if (opt.tree_iter_stats && tree) o << "#define WOST_TREE_ITER_STATS 1\n";   // study builds: loop counters
+    if (opt.vote_stats) o << "#define WOST_VOTE_STATS 1\n";                      // study builds: vote counters
     if (tree && tree_stage >= 1) o << "#define WOST_TREE_STAGED 1\n";    // every record in LDS
     if (tree && tree_stage >= 2) o << "#define WOST_TREE_VSTAGED 1\n";   // and the Neumann vertices
     if (opt.tree_qmargin >= 0) o << "#define WOST_TREE_QMARGIN " << opt.tree_qmargin << "\n";
@@ -784,7 +788,8 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
     o << "    __device__ __forceinline__ float alpha(float x, float y) const {\n"
       << (fA.present ? value_body(fA, terms, factors) : "        return 1.0f;\n") << "    }\n";
     o << "    __device__ __forceinline__ wost::Jet alpha_jet(float x, float y) const {\n"
-      << (fA.present ? jet_body(fA, terms, factors, (fA.flags & WOST_FIELD_DETACHED) ? nullptr : "alpha", xf) : "        return wost::jet_const(1.0f);\n") << "    }\n";
+      << (fA.present ? jet_body(fA, terms, factors, (fA.flags & WOST_FIELD_DETACHED) ? nullptr : "alpha",
+                                    xf | (opt.vote_stats ? kVoteStatsFlag : 0)) : "        return wost::jet_const(1.0f);\n") << "    }\n";
     o << "    __device__ __forceinline__ bool detached() const { return "
       << ((fA.flags & WOST_FIELD_DETACHED) ? "true" : "false") << "; }\n";
     o << "    __device__ __forceinline__ float sigma_bar() const { return " << lit(hdr.sigma_bar) << "; }\n";
@@ -1006,6 +1011,23 @@ int pending_code(const std::string& key, bool wait, std::vector<char>* code) {
 }
 
 }  // namespace
+
+bool jit_kernel_global(hipFunction_t fn, const char* name, void** dptr, size_t* bytes) {
+    std::lock_guard<std::mutex> lock(g_mu);
+    for (const auto& kv : g_modules) {
+        if (kv.second.fn != fn) continue;
+        hipDeviceptr_t p = nullptr;
+        size_t n = 0;
+        if (hipModuleGetGlobal(&p, &n, kv.second.mod, name) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        *dptr = p;
+        *bytes = n;
+        return true;
+    }
+    return false;
+}
 
 bool JitTicket::done() const {
     if (!p) return true;

@@ -81,6 +81,9 @@ JitTry jit_try_kernel(const Options& opt, int device, const std::string& source,
 bool jit_compile_host(const Options& opt, const std::string& source, const std::string& arch,
                       std::vector<char>* code, std::string* err, bool* in_helper);
 // Whether the compile helper is installed next to this library (and runs).
+// Study builds (option vote_stats): the device address and size of a module-scope variable
+// of the loaded module that `fn` belongs to; false when it has none of that name.
+bool jit_kernel_global(hipFunction_t fn, const char* name, void** dptr, size_t* bytes);
 bool jit_helper_available();
 // Starts finding the helper's compiler in the background (once per process; wost_create),
 // so that the first compile does not wait for the helper's start.

@@ -52,6 +52,7 @@ const Spec kSpecs[] = {
     {"lds_pad_bytes", &Options::lds_pad_bytes, nullptr, 0, 1 << 17, false, false, "WOST_LDS_PAD_BYTES"},
     {"exp_flags", &Options::exp_flags, nullptr, 0, 0x3FFFFFFF, true, true, "WOST_EXP_FLAGS"},
     {"tree_iter_stats", &Options::tree_iter_stats, nullptr, 0, 1, true, true, "WOST_TREE_ITER_STATS"},
+    {"vote_stats", &Options::vote_stats, nullptr, 0, 1, true, true, "WOST_VOTE_STATS"},
 };
 
 const Spec* find(const char* name) {

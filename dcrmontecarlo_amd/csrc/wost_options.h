@@ -12,7 +12,8 @@
 // Study builds (make study: build/libwost_study.so, -DWOST_STUDY) additionally seed the
 // options from the A/B environment variables of tools/ (WOST_POOL_SLOTS, WOST_CHUNK0, ...)
 // and accept the result-changing ablations (WOST_EXP_FLAGS, timing studies only: their
-// walks are wrong by design) and the tree queries' loop counters (WOST_TREE_ITER_STATS).
+// walks are wrong by design), the tree queries' loop counters (WOST_TREE_ITER_STATS) and
+// the wave votes' counters (WOST_VOTE_STATS, tools/vote_table.py).
 #pragma once
 
 #include <cstddef>
@@ -68,6 +69,7 @@ struct Options {
     // study builds only (never settable in the product library)
     int exp_flags = 0;              // result-changing ablations (wost_jit.cpp)
     int tree_iter_stats = 0;        // the tree queries' loop counters
+    int vote_stats = 0;             // the wave votes' entry and lane counters (wost_device.h WOST_VOTE)
     std::string jit_sched;          // -mllvm -amdgpu-sched-strategy=<...>
 };
 

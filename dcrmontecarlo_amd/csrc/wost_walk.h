@@ -979,6 +979,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     const int lane = threadIdx.x & 63;
     const uint64_t lanebit = 1ull << lane;
     const uint64_t lanes_below = lanebit - 1ull;
+#if defined(WOST_VOTE_STATS)   // study build: the wave votes' counters (wost_device.h WOST_VOTE)
+    vote_begin();
+#endif
 
     // wave-uniform work-queue state
     uint64_t c_next = 0, c_end = 0;
@@ -1250,6 +1253,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
 #if defined(WOST_TREE_ITER_STATS)
         ic_arr[14] += 1u;
 #endif
+        WOST_VOTE(0, stepping);
         WOST_PHASE("dirichlet_distance");
         float dd = fld.dirichlet_distance(dP, A.nd, px, py);        // :208
         if (WOST_ABL_DUP & 1) dd = dup_merge(dd, fld.dirichlet_distance(dP, A.nd, dup_opq(px), py));
@@ -1409,17 +1413,15 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 yy = py + rs * sn;
                 const float e1x = yx - px, e1y = yy - py;
                 const float e2x = xnx - px, e2y = xny - py;
-                // :248 compares the two norms. sqrt is monotone, so sqrt(a2) > sqrt(b2)
-                // needs a2 > b2 (rare: only Neumann hits make the next point closer);
-                // only then evaluate the reference's exact comparison.
+                // :248 compares the two norms. a2 > b2 is not rare: a Neumann "hit" is any
+                // ray whose line crosses a segment (Q1), its point within ~1 of x while the
+                // sample radius is of order r, so a2 > b2 on 13.9% of C4's lane-steps (2.1%
+                // of C3's) and some lane of nearly every wave-step has it. The ratio decides
+                // all of them without a square root; only the ~2^-19 wide band above b2
+                // (no lane-step of either sample) evaluates the reference's comparison.
                 const float a2 = e1x * e1x + e1y * e1y, b2 = e2x * e2x + e2y * e2y;
                 if (WOST_PHILOX_AHEAD == 3) WOST_PIN_U4(rn_ahead);
-                // a real branch (the compiler otherwise evaluates both correctly rounded
-                // square roots for every lane and selects, ~35 instructions per step)
-                if (WOST_ANY(a2 > b2)) {
-                    WOST_NO_SPECULATION();
-                    if (a2 > b2) clipped = sqrtf(a2) > sqrtf(b2);
-                }
+                clipped = norm_greater(a2, b2);
                 if (clipped) { yx = xnx; yy = xny; }
             }
             if (DELTA) {
@@ -1554,6 +1556,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         dD = dd;   // the loop tests the distance of the pre-step point (quirk Q7)
         WOST_PHASE("loop_head");
     }
+#if defined(WOST_VOTE_STATS)
+    vote_end();   // (every lane is here)
+#endif
     if (kWaveStats) {   // the wave's longest walk (every lane is here)
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {

@@ -500,7 +500,7 @@ int wost_set_segment_tree(wost_handle* h, int32_t min_segments, int32_t leaf_seg
  * chunk0,
  * chunk_min, chunk_max, adaptive_chunk, grid_blocks_per_cu, lds_pad_bytes.
  * WOST_ERR_INVALID_ARG for an unknown name or a value out of range; WOST_ERR_UNSUPPORTED
- * for a study-build-only name (exp_flags, tree_iter_stats) in the product library. The
+ * for a study-build-only name (exp_flags, tree_iter_stats, vote_stats) in the product library. The
  * product library reads no environment variable that changes a kernel or a result
  * (study builds, build/libwost_study.so, seed options from the tools' A/B variables). */
 int wost_set_option(wost_handle* h, const char* name, double value);
