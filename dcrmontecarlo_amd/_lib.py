@@ -27,6 +27,7 @@ WOST_COMM_ID_BYTES = 128
 WOST_COMM_SUM, WOST_COMM_MAX = 0, 1
 WOST_BLOCK_WALKS = 4096
 WOST_MAX_SOURCES = 16   # include/wost.h
+WOST_MAX_POINT_CHARGES = 32   # include/wost.h
 WOST_TRIG = {"auto": 0, "exact": 1, "fast": 2}   # include/wost.h wost_trig
 WOST_SAMPLER_TABLE_N = 4097
 COMPAT = {"reference": 0, "fixed": 1}
@@ -48,6 +49,10 @@ class WostField(ctypes.Structure):
     _fields_ = [("terms", POINTER(WostTerm)), ("n_terms", c_int32),
                 ("factors", POINTER(WostFactor)), ("n_factors", c_int32), ("flags", c_int32),
                 ("grid", POINTER(c_float)), ("n_grid", c_int64)]
+
+
+class WostPointCharge(ctypes.Structure):
+    _fields_ = [("x", c_float), ("y", c_float), ("strength", c_float), ("source", c_int32)]
 
 
 class WostPolyline(ctypes.Structure):
@@ -124,6 +129,13 @@ def _load():
         "wost_num_sources": (c_int32, [H, POINTER(c_int32)]),
         "wost_set_wavenumbers": (c_int32, [H, POINTER(c_double), c_int32]),
         "wost_num_channels": (c_int32, [H, POINTER(c_int32)]),
+        "wost_set_point_sources": (c_int32, [H, POINTER(WostPointCharge), c_int32, c_int32]),
+        "wost_point_sources_info": (c_int32, [H, POINTER(c_int32), POINTER(c_uint64)]),
+        "wost_ball_greens": (c_int32, [c_double, POINTER(c_float), POINTER(c_float), c_int64, POINTER(c_float)]),
+        "wost_point_visible": (c_int32, [POINTER(WostPolyline), POINTER(c_float), POINTER(c_int32), POINTER(c_float),
+                                         c_int64, POINTER(c_uint8)]),
+        "wost_kernel_source_points": (c_int32, [POINTER(WostProblem), c_int32, c_int32, c_int32, ctypes.c_char_p,
+                                                c_int64, POINTER(c_int64)]),
         "wost_solve_range": (c_int32, [H, POINTER(c_float), c_int64, c_int64, c_int64, c_int64, c_int32, c_float,
                                        c_uint64, POINTER(c_double), POINTER(c_double), POINTER(c_float),
                                        POINTER(c_uint32)]),

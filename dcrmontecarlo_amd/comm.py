@@ -448,6 +448,10 @@ def solve_sources_distributed(solver, comm: Communicator, points, sources, nWalk
     every rank, bitwise those of a one-GPU solve_sources."""
     from .solvers.WoStSolver import SolveStats, _stats_of_multi
 
+    if any(hasattr(s, "charges") for s in sources):
+        raise NotImplementedError("solve_sources_distributed takes source fields; for point sources call "
+                                  "solver.set_point_sources(...) and solve_distributed (one source), or "
+                                  "wost_solve_distributed through the C ABI")
     p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 2))
     fields = solver.source_fields(sources)
     stats, steps, lsteps, kms, tms = [], 0, 0, 0.0, 0.0

@@ -192,6 +192,15 @@ struct wost_handle {
     int n_wavenumbers = 0;
     float k2[WOST_MAX_SOURCES] = {};
     int channels() const { return (n_wavenumbers > 0 ? n_wavenumbers : 1) * n_sources; }
+    // point sources (wost_set_point_sources): the charges (n_sources counts their source
+    // channels then), the Neumann segment(s) each lies on ([2 n], -1: none) and their device
+    // image (WalkArgs::charges, kChargeWords words)
+    std::vector<wost_point_charge> charges;
+    std::vector<int32_t> charge_seg;
+    float* d_charges = nullptr;
+    int32_t* d_point_code = nullptr;   // boundary_code of the query points (WalkArgs::point_code)
+    int64_t point_code_cap = 0;
+    bool has_source() const { return fields[SLOT_F].present || !charges.empty(); }
     bool delta = false;
     double sigma_bar = 0.0;
     Program prog;
@@ -309,7 +318,8 @@ int jit_source(const wost_handle* h, const Program& prog, int mode, bool record,
     }
     *src = jit_generate(h->opt, mode, *prog.hdr(), prog.terms(), prog.factors(), h->dverts.data(),
                         (int)(h->dverts.size() / 2), h->nverts.data(), nn, record, ns, block,
-                        phi.empty() ? nullptr : phi.data(), global_polylines, tree_stage, exact_trig_of(h), nk);
+                        phi.empty() ? nullptr : phi.data(), global_polylines, tree_stage, exact_trig_of(h), nk,
+                        (int)h->charges.size());
     return WOST_OK;
 }
 
@@ -319,8 +329,10 @@ int jit_source(const wost_handle* h, const Program& prog, int mode, bool record,
 int jit_key(const wost_handle* h, int mode, bool record, int ns, int block, bool global_polylines, int tree_stage) {
     const bool exact = exact_trig_of(h);
     const int nk = mode_delta(mode) ? h->n_wavenumbers : 0;
-    return ((((((2 * mode + (record ? 1 : 0)) * (WOST_MAX_SOURCES + 1) + ns) * (WOST_MAX_SOURCES + 1) + nk) * 3 +
-              tree_stage) * 17 + block / 64) * 2 + (global_polylines ? 1 : 0)) * 2 + (exact ? 1 : 0);
+    const int pc = (int)h->charges.size();   // (the count only: the charges are run-time data)
+    return (((((((2 * mode + (record ? 1 : 0)) * (WOST_MAX_SOURCES + 1) + ns) * (WOST_MAX_SOURCES + 1) + nk) * 3 +
+               tree_stage) * 17 + block / 64) * 2 + (global_polylines ? 1 : 0)) * 2 + (exact ? 1 : 0)) *
+               (WOST_MAX_POINT_CHARGES + 1) + pc;
 }
 
 // jit_kernel without blocking on a compile (option jit_race): kReady with the handle's
@@ -591,7 +603,7 @@ int walk_mode_src(const wost_handle* h, bool src) {
     return src ? MODE_POISSON : MODE_DIRICHLET;
 }
 
-int walk_mode(const wost_handle* h) { return walk_mode_src(h, h->fields[SLOT_F].present); }
+int walk_mode(const wost_handle* h) { return walk_mode_src(h, h->has_source()); }
 
 int ensure_tree(wost_handle* h) {
     if (h->tree_ready) return WOST_OK;
@@ -698,7 +710,8 @@ void wost_destroy(wost_handle* h) {
     if (!h) return;
     if (h->device >= 0) (void)hipSetDevice(h->device);
     void* ptrs[] = {h->d_dverts, h->d_nverts, h->d_table, h->d_prog, h->d_counter, h->d_val,
-                    h->d_steps, h->d_stage, h->d_bstats, h->d_tree, h->d_seg_phi, h->d_point_alpha, h->d_pool};
+                    h->d_steps, h->d_stage, h->d_bstats, h->d_tree, h->d_seg_phi, h->d_point_alpha, h->d_pool,
+                    h->d_charges, h->d_point_code};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -857,6 +870,12 @@ int wost_set_field(wost_handle* h, int32_t slot, const wost_field* field) {
     HostField hf;
     int rc = convert_field(field, hf, s == SLOT_G ? "boundary" : "source");
     if (rc != WOST_OK) return rc;
+    if (s == SLOT_F && !h->charges.empty()) {   // point sources: no source field beside them
+        if (hf.present)
+            return fail(WOST_ERR_INVALID_ARG, "the handle has point sources (wost_set_point_sources): clear them "
+                                              "before setting a source field");
+        return WOST_OK;
+    }
     h->fields[s] = hf;
     if (s == SLOT_F) {   // setSourceTerm: back to a single source
         for (int k = SLOT_EXTRA; k < N_FIELDS; ++k) h->fields[k] = HostField();
@@ -1042,6 +1061,9 @@ int choose_kernel(wost_handle* h, int mode, int64_t n_points, bool record, int n
     auto lookup = [&]() -> int {
         kc->jfn = jit_kernel(h, mode, record, n_src, ks.block, ks.gpoly, ks.stage(), &kc->jit_ms);
         if (!kc->jfn) {   // the precompiled kernels run 256-thread workgroups, no staged tree, one channel
+            if (!h->charges.empty())
+                return fail(WOST_ERR_UNSUPPORTED, "point sources need the field-specialised kernel%s%s",
+                            h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
             if (ns > 1)
                 return fail(WOST_ERR_UNSUPPORTED,
                             "multi-source and multi-wavenumber solves need the field-specialised kernel%s%s",
@@ -1102,7 +1124,7 @@ int check_request(const wost_handle* h, const SolveRequest& rq, SolveRanges* ran
         return fail(rc, "%s", msg);
     for (int64_t i = 0; i < 2 * n_points; ++i)
         if (!std::isfinite(points[i])) return fail(WOST_ERR_INVALID_ARG, "solve point %lld is not finite", (long long)(i / 2));
-    if (h->delta && !h->fields[SLOT_F].present)
+    if (h->delta && !h->has_source())
         return fail(WOST_ERR_INVALID_ARG,
                     "delta tracking (sigma/alpha given) needs a source term: the reference raises "
                     "UnboundLocalError at solvers/WoStSolver.py:281 (quirk Q14)");
@@ -1192,6 +1214,7 @@ WalkArgs fill_walk_args(const wost_handle* h, const SolveRequest& rq, int mode, 
     a.rec_stride = (int32_t)((int64_t)rq.max_steps + 1);
     a.exact_trig = exact_trig_of(h) ? 1 : 0;
     for (int j = 0; j < h->n_wavenumbers; ++j) a.k2[j] = h->k2[j];   // (the rest 0)
+    a.charges = h->charges.empty() ? nullptr : h->d_charges;
     if (mode_tree(mode)) {
         a.tree = reinterpret_cast<const float4*>(h->d_tree);
         a.tree_first_leaf = h->tree.first_leaf;
@@ -1212,7 +1235,8 @@ WalkArgs fill_walk_args(const wost_handle* h, const SolveRequest& rq, int mode, 
 // (a parked walk holds one attenuation: launches of several wavenumbers run without pools)
 int setup_pools(wost_handle* h, int mode, int n_src, int blocks_per_cu, WalkArgs* a) {
     const Options& O = h->opt;
-    if (!mode_tree(mode) || O.tree_pool == 0 || h->nverts.size() < 4 || h->n_wavenumbers > 1) return WOST_OK;
+    if (!mode_tree(mode) || O.tree_pool == 0 || h->nverts.size() < 4 || h->n_wavenumbers > 1 || !h->charges.empty())
+        return WOST_OK;
     float x0 = h->nverts[0], x1 = x0, y0 = h->nverts[1], y1 = y0;
     for (size_t i = 2; i + 1 < h->nverts.size(); i += 2) {
         x0 = std::min(x0, h->nverts[i]); x1 = std::max(x1, h->nverts[i]);
@@ -1249,6 +1273,124 @@ int launch_point_alpha_for(wost_handle* h, int mode, hipFunction_t jfn, int64_t 
     }
     a->point_alpha = h->d_point_alpha;
     return WOST_OK;
+}
+
+// ---- point sources: the host's geometry (wost_set_point_sources, setup_point_sources) ----
+
+// The Neumann segment(s) the point lies on: up to two (a vertex), -1 for none. "On" is
+// within 2^-21 of the summed coordinate magnitudes (a couple of float32 ulps).
+void segments_at(const float* nv, int nn, float x, float y, int32_t* s0, int32_t* s1) {
+    *s0 = *s1 = -1;
+    for (int i = 0; i + 1 < nn; ++i) {
+        const double ax = nv[2 * i], ay = nv[2 * i + 1], bx = nv[2 * i + 2], by = nv[2 * i + 3];
+        const double ux = bx - ax, uy = by - ay, uu = ux * ux + uy * uy;
+        double t = uu > 0.0 ? ((x - ax) * ux + (y - ay) * uy) / uu : 0.0;
+        t = std::min(1.0, std::max(0.0, t));
+        const double dx = x - (ax + t * ux), dy = y - (ay + t * uy);
+        const double tol = 0x1p-21 * (std::fabs(x) + std::fabs(y) + std::fabs(ax) + std::fabs(ay) + std::fabs(bx) +
+                                      std::fabs(by));
+        if (std::sqrt(dx * dx + dy * dy) <= tol) {
+            if (*s0 < 0) *s0 = i;
+            else if (*s1 < 0) *s1 = i;
+        }
+    }
+}
+
+// Even-odd test of (x, y) against the closed curve the Dirichlet and Neumann polylines form.
+bool inside_domain(const wost_handle* h, double x, double y) {
+    bool in = false;
+    auto scan = [&](const std::vector<float>& v) {
+        for (size_t i = 0; i + 3 < v.size(); i += 2) {
+            const double ax = v[i], ay = v[i + 1], bx = v[i + 2], by = v[i + 3];
+            if ((ay > y) != (by > y) && x < ax + (y - ay) * (bx - ax) / (by - ay)) in = !in;
+        }
+    };
+    scan(h->dverts);
+    scan(h->nverts);
+    return in;
+}
+
+// boundary_code of a point on Neumann segment seg: which of its normals points into the
+// domain, from even-odd tests a thousandth of its length off its midpoint. 0 when the two
+// sides do not differ (the polylines do not close the domain).
+int32_t code_of_segment(const wost_handle* h, int seg) {
+    const double ax = h->nverts[2 * seg], ay = h->nverts[2 * seg + 1];
+    const double bx = h->nverts[2 * seg + 2], by = h->nverts[2 * seg + 3];
+    const double mx = 0.5 * (ax + bx), my = 0.5 * (ay + by), d = 1e-3;
+    const double lx = -(by - ay) * d, ly = (bx - ax) * d;   // the left normal, scaled
+    const bool left = inside_domain(h, mx + lx, my + ly), right = inside_domain(h, mx - lx, my - ly);
+    if (left == right) return 0;
+    return boundary_code(seg, right);
+}
+
+// The device image of the handle's charges (WalkArgs::charges), alpha left at 1.
+int upload_charges(wost_handle* h) {
+    std::vector<float> w((size_t)kChargeWords, 0.0f);
+    for (size_t p = 0; p < h->charges.size(); ++p) {
+        const wost_point_charge& c = h->charges[p];
+        w[CHG_XY + 2 * p] = c.x;
+        w[CHG_XY + 2 * p + 1] = c.y;
+        w[CHG_Q + p] = c.strength;
+        w[CHG_ALPHA + p] = 1.0f;
+        std::memcpy(&w[CHG_SOURCE + p], &c.source, sizeof(int32_t));
+        std::memcpy(&w[CHG_SEG0 + p], &h->charge_seg[2 * p], sizeof(int32_t));
+        std::memcpy(&w[CHG_SEG1 + p], &h->charge_seg[2 * p + 1], sizeof(int32_t));
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->d_charges) HIP_TRY(hipMalloc(&h->d_charges, sizeof(float) * (size_t)kChargeWords));
+    HIP_TRY(hipMemcpy(h->d_charges, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
+    return WOST_OK;
+}
+
+// A point-source solve's per-solve data: alpha at the charges with the walk kernel's own
+// fields (delta tracking; the kernel that evaluates it at the query points), and the query
+// points' boundary codes (a Neumann polyline).
+int setup_point_sources(wost_handle* h, int mode, const SolveRequest& rq, WalkArgs* a) {
+    if (h->charges.empty()) return WOST_OK;
+    if (mode_delta(mode)) {
+        if (!h->jit_alpha_fn) return fail(WOST_ERR_UNSUPPORTED, "point sources need the field-specialised kernel");
+        const float2* pts = reinterpret_cast<const float2*>(h->d_charges + CHG_XY);
+        long long n = (long long)h->charges.size();
+        float* out = h->d_charges + CHG_ALPHA;
+        const char* prog = h->d_prog;
+        void* args[] = {&prog, &pts, &n, &out};
+        HIP_TRY(hipModuleLaunchKernel(h->jit_alpha_fn, 1, 1, 1, 256, 1, 1, 0, h->stream, args, nullptr));
+    }
+    if (!mode_neu(mode) || rq.n_points <= 0) return WOST_OK;
+    const int nn = (int)(h->nverts.size() / 2);
+    std::vector<int32_t> code((size_t)rq.n_points, 0);
+    std::vector<int32_t> seg_code((size_t)std::max(nn - 1, 0), INT32_MIN);   // (each segment's, found once)
+    for (int64_t i = 0; i < rq.n_points; ++i) {
+        int32_t s0, s1;
+        segments_at(h->nverts.data(), nn, rq.points[2 * i], rq.points[2 * i + 1], &s0, &s1);
+        if (s0 < 0) continue;
+        if (seg_code[s0] == INT32_MIN) seg_code[s0] = code_of_segment(h, s0);
+        if (seg_code[s0] == 0)
+            return fail(WOST_ERR_INVALID_ARG,
+                        "solve point %lld lies on Neumann segment %d, whose inner side cannot be told: with point "
+                        "sources the Dirichlet and Neumann polylines must close the domain", (long long)i, s0);
+        code[(size_t)i] = seg_code[s0];
+    }
+    if (int rc = ensure_cap(h->d_point_code, h->point_code_cap, rq.n_points)) return rc;
+    HIP_TRY(hipMemcpy(h->d_point_code, code.data(), sizeof(int32_t) * code.size(), hipMemcpyHostToDevice));
+    a->point_code = h->d_point_code;
+    return WOST_OK;
+}
+
+// FNV-1a 64 of the charges and their source count.
+uint64_t charges_checksum(const wost_handle* h) {
+    if (h->charges.empty()) return 0;
+    uint64_t hsh = 1469598103934665603ull;
+    auto eat = [&](const void* p, size_t n) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        for (size_t i = 0; i < n; ++i) hsh = (hsh ^ b[i]) * 1099511628211ull;
+    };
+    const int32_t ns = h->n_sources;
+    eat(&ns, sizeof(ns));
+    for (const wost_point_charge& c : h->charges) {
+        eat(&c.x, sizeof(float)); eat(&c.y, sizeof(float)); eat(&c.strength, sizeof(float)); eat(&c.source, sizeof(int32_t));
+    }
+    return hsh;
 }
 
 // One launch's walks (wost_launch.h next_batch) in the kernel's arguments.
@@ -1367,8 +1509,11 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
 
     HIP_TRY(hipSetDevice(h->device));
     if ((rc = upload_program(h)) != WOST_OK) return rc;
-    if (h->fields[SLOT_F].present && (rc = ensure_table(h)) != WOST_OK) return rc;
+    if (h->has_source() && (rc = ensure_table(h)) != WOST_OK) return rc;
     if (mode_tree(mode) && (rc = ensure_tree(h)) != WOST_OK) return rc;
+    if (out.records && !h->charges.empty())
+        return fail(WOST_ERR_UNSUPPORTED, "wost_solve_history does not record point sources (a step scores every "
+                                          "charge in its ball: there is no sample point)");
 
     h->timing = wost_timing{};
     if (out.point_stats) std::fill(out.point_stats, out.point_stats + row * n_points, 0.0);
@@ -1417,6 +1562,7 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
     WalkArgs a = fill_walk_args(h, rq, mode, kc, d_rec);
     if ((rc = setup_pools(h, mode, n_src, kc.blocks_per_cu, &a)) != WOST_OK) return rc;
     if ((rc = launch_point_alpha_for(h, mode, kc.jfn, n_points, &a)) != WOST_OK) return rc;
+    if ((rc = setup_point_sources(h, mode, rq, &a)) != WOST_OK) return rc;
 
     LaunchIn shape_in;
     shape_in.short_walks = !mode_neu(mode);
@@ -1737,7 +1883,8 @@ int wost_solve(wost_handle* h, const float* points, int64_t n_points, int64_t W,
     out.walk_values = walk_values; out.walk_steps = walk_steps;
     // a whole single-source solve may start on the precompiled kernel while its specialised
     // one compiles (solve_race)
-    if (h && h->jit_enabled && h->opt.jit_race && h->channels() == 1 && n_points > 0 && W > 0 && block_begin == 0 &&
+    if (h && h->jit_enabled && h->opt.jit_race && h->channels() == 1 && h->charges.empty() && n_points > 0 && W > 0 &&
+        block_begin == 0 &&
         block_end == rq.block_end && max_steps >= 0 && eps == eps)
         return solve_race(h, rq, out);
     rq.block_begin = block_begin;
@@ -1801,6 +1948,9 @@ int wost_solve_multi(wost_handle* h, const float* points, int64_t n_points, int6
 
 int wost_set_sources(wost_handle* h, const wost_field* const* sources, int32_t n) {
     if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    if (!h->charges.empty())
+        return fail(WOST_ERR_INVALID_ARG, "the handle has point sources (wost_set_point_sources): clear them before "
+                                          "setting source fields");
     std::vector<HostField> f(N_FIELDS);
     int rc = fields_with_sources(h, sources, n, f.data());
     if (rc != WOST_OK) return rc;
@@ -1817,6 +1967,8 @@ int wost_set_sources(wost_handle* h, const wost_field* const* sources, int32_t n
 int wost_prepare_sources(wost_handle* h, const wost_field* const* sources, int32_t n, int64_t n_points) {
     if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
     if (n_points < 1) return fail(WOST_ERR_INVALID_ARG, "n_points must be >= 1 (got %lld)", (long long)n_points);
+    if (!h->charges.empty())
+        return fail(WOST_ERR_INVALID_ARG, "the handle has point sources (wost_set_point_sources): clear them first");
     std::vector<HostField> f(N_FIELDS);
     int rc = fields_with_sources(h, sources, n, f.data());
     if (rc != WOST_OK) return rc;
@@ -1843,10 +1995,48 @@ int wost_prepare_sources(wost_handle* h, const wost_field* const* sources, int32
     return WOST_OK;
 }
 
-int wost_kernel_source_channels(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
-                                int32_t n_wavenumbers, char* out, int64_t capacity, int64_t* length) {
+}  // extern "C"
+
+namespace {
+// wost_set_point_sources' argument checks (shared with wost_kernel_source_points, which has
+// counts only: charges == nullptr skips the per-charge checks).
+int check_point_sources(const wost_handle* h, const wost_point_charge* charges, int32_t n, int32_t n_sources) {
+    if (h->compat != WOST_COMPAT_FIXED)
+        return fail(WOST_ERR_UNSUPPORTED,
+                    "point sources need compat=\"fixed\": the reference estimator ties the source sample to the step's "
+                    "direction (Q13) and draws it without the Jacobian (Q3), so it has no exact counterpart");
+    if (n > WOST_MAX_POINT_CHARGES)
+        return fail(WOST_ERR_INVALID_ARG, "%d point charges exceed %d per launch", n, WOST_MAX_POINT_CHARGES);
+    if (n_sources < 1 || n_sources > n)
+        return fail(WOST_ERR_INVALID_ARG, "need 1 <= n_sources <= n (every source has a charge), got %d sources of %d "
+                                          "charges", n_sources, n);
+    const int nk = h->n_wavenumbers > 0 ? h->n_wavenumbers : 1;
+    if ((int64_t)n_sources * nk > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "%d sources x %d wavenumbers exceed %d channels", n_sources, nk, WOST_MAX_SOURCES);
+    if (h->fields[SLOT_F].present)
+        return fail(WOST_ERR_INVALID_ARG, "the handle has a source field: point sources cannot be mixed with it "
+                                          "(create the solver without a source)");
+    if (!charges) return WOST_OK;
+    std::vector<int> count((size_t)n_sources, 0);
+    for (int p = 0; p < n; ++p) {
+        const wost_point_charge& c = charges[p];
+        if (!std::isfinite(c.x) || !std::isfinite(c.y) || !std::isfinite(c.strength))
+            return fail(WOST_ERR_INVALID_ARG, "point charge %d has a non-finite position or strength", p);
+        if (c.source < 0 || c.source >= n_sources)
+            return fail(WOST_ERR_INVALID_ARG, "point charge %d: source %d outside [0, %d)", p, c.source, n_sources);
+        ++count[(size_t)c.source];
+    }
+    for (int s = 0; s < n_sources; ++s)
+        if (count[(size_t)s] == 0) return fail(WOST_ERR_INVALID_ARG, "source %d has no point charge", s);
+    return WOST_OK;
+}
+
+// wost_kernel_source_channels, and with n_charges > 0 wost_kernel_source_points (n_sources is
+// then the charges' source count, sources NULL).
+int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
+                       int32_t n_wavenumbers, int32_t n_charges, char* out, int64_t capacity, int64_t* length) {
     if (!pb || !length) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
-    if (n_sources < 0 || n_sources > WOST_MAX_SOURCES || (n_sources > 0 && !sources))
+    if (n_sources < 0 || n_sources > WOST_MAX_SOURCES || (n_charges == 0 && n_sources > 0 && !sources))
         return fail(WOST_ERR_INVALID_ARG, "need 0..%d sources", WOST_MAX_SOURCES);
     if (n_wavenumbers < 0 || n_wavenumbers * std::max(n_sources, 1) > WOST_MAX_SOURCES)
         return fail(WOST_ERR_INVALID_ARG, "need sources x wavenumbers <= %d channels", WOST_MAX_SOURCES);
@@ -1859,7 +2049,14 @@ int wost_kernel_source_channels(const wost_problem* pb, const wost_field* const*
     }
     h->n_wavenumbers = n_wavenumbers;
     int ns = 1;
-    if (n_sources >= 1) {   // wost_set_sources' fields, without a device
+    if (n_charges > 0) {   // wost_set_point_sources' checks and counts, without a device
+        if ((rc = check_point_sources(h, nullptr, n_charges, n_sources)) != WOST_OK) {
+            delete h;
+            return rc;
+        }
+        h->charges.assign((size_t)n_charges, wost_point_charge{0.f, 0.f, 0.f, 0});
+        h->n_sources = ns = n_sources;
+    } else if (n_sources >= 1) {   // wost_set_sources' fields, without a device
         for (int k = 0; k < n_sources; ++k) {
             HostField hf;
             if (!sources[k] || (rc = convert_field(sources[k], hf, "source")) != WOST_OK) {
@@ -1894,7 +2091,7 @@ int wost_kernel_source_channels(const wost_problem* pb, const wost_field* const*
     const std::string src = jit_generate(h->opt, mode, *h->prog.hdr(), h->prog.terms(), h->prog.factors(), h->dverts.data(),
                                          (int)(h->dverts.size() / 2), h->nverts.data(), nn, false, ns, block,
                                          phi.empty() ? nullptr : phi.data(), false, stage, exact_trig_of(h),
-                                         mode_delta(mode) ? n_wavenumbers : 0);
+                                         mode_delta(mode) ? n_wavenumbers : 0, n_charges);
     delete h;
     *length = (int64_t)src.size();
     if (out && capacity > 0) {
@@ -1903,6 +2100,20 @@ int wost_kernel_source_channels(const wost_problem* pb, const wost_field* const*
         out[n] = '\0';
     }
     return WOST_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int wost_kernel_source_channels(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
+                                int32_t n_wavenumbers, char* out, int64_t capacity, int64_t* length) {
+    return kernel_source_impl(pb, sources, n_sources, n_wavenumbers, 0, out, capacity, length);
+}
+
+int wost_kernel_source_points(const wost_problem* pb, int32_t n_charges, int32_t n_sources, int32_t n_wavenumbers,
+                              char* out, int64_t capacity, int64_t* length) {
+    if (n_charges < 1) return fail(WOST_ERR_INVALID_ARG, "need n_charges >= 1");
+    return kernel_source_impl(pb, nullptr, n_sources, n_wavenumbers, n_charges, out, capacity, length);
 }
 
 int wost_kernel_source_sources(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
@@ -1939,6 +2150,71 @@ int wost_set_wavenumbers(wost_handle* h, const double* k2, int32_t n) {
 int wost_num_channels(const wost_handle* h, int32_t* n_channels) {
     if (!h || !n_channels) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
     *n_channels = h->channels();
+    return WOST_OK;
+}
+
+int wost_set_point_sources(wost_handle* h, const wost_point_charge* charges, int32_t n, int32_t n_sources) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    if (n < 0 || (n > 0 && !charges)) return fail(WOST_ERR_INVALID_ARG, "need n >= 0 point charges");
+    if (n == 0) {
+        if (!h->charges.empty()) h->n_sources = 1;
+        h->charges.clear();
+        h->charge_seg.clear();
+        return WOST_OK;
+    }
+    if (int rc = check_point_sources(h, charges, n, n_sources)) return rc;
+    std::vector<int32_t> seg(2 * (size_t)n, -1);
+    const int nn = (int)(h->nverts.size() / 2);
+    for (int p = 0; p < n; ++p) segments_at(h->nverts.data(), nn, charges[p].x, charges[p].y, &seg[2 * p], &seg[2 * p + 1]);
+    const std::vector<wost_point_charge> old_charges = h->charges;
+    const std::vector<int32_t> old_seg = h->charge_seg;
+    h->charges.assign(charges, charges + n);
+    h->charge_seg = seg;
+    if (int rc = upload_charges(h)) {   // (a refused set changes nothing)
+        h->charges = old_charges;
+        h->charge_seg = old_seg;
+        return rc;
+    }
+    for (int k = SLOT_EXTRA; k < N_FIELDS; ++k) h->fields[k] = HostField();
+    h->n_sources = n_sources;
+    h->prog_dirty = true;
+    return upload_program(h);
+}
+
+int wost_point_sources_info(const wost_handle* h, int32_t* n, uint64_t* checksum) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    if (n) *n = (int32_t)h->charges.size();
+    if (checksum) *checksum = charges_checksum(h);
+    return WOST_OK;
+}
+
+int wost_ball_greens(double sigma_bar, const float* r, const float* R, int64_t n, float* out) {
+    if (!(sigma_bar >= 0.0) || !std::isfinite(sigma_bar) || n < 0 || (n > 0 && (!r || !R || !out)))
+        return fail(WOST_ERR_INVALID_ARG, "need a finite sigma_bar >= 0 and n >= 0 radii");
+    const float sqrt_sb = (float)std::sqrt(sigma_bar);   // the kernels' constant (build_program)
+    for (int64_t i = 0; i < n; ++i)
+        out[i] = sigma_bar > 0.0 ? ball_greens_screened(r[i], R[i], sqrt_sb) : ball_greens(r[i], R[i]);
+    return WOST_OK;
+}
+
+int wost_point_visible(const wost_polyline* neumann, const float* points, const int32_t* point_segments,
+                       const float* charges, int64_t n, uint8_t* out) {
+    if (!neumann || !neumann->xy || neumann->n_vertices < 2) return fail(WOST_ERR_INVALID_ARG, "bad polyline");
+    if (n < 0 || (n > 0 && (!points || !charges || !out))) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
+    const int nv = neumann->n_vertices;
+    const float2* v = reinterpret_cast<const float2*>(neumann->xy);
+    auto nearest = [&](float ox, float oy, float ex, float ey, float len) {
+        return intersect_polylines_ray(v, nv, ox, oy, ex, ey, len);
+    };
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t code = point_segments ? point_segments[i] : 0;
+        if ((code < 0 ? -(int64_t)code : (int64_t)code) > nv - 1)
+            return fail(WOST_ERR_INVALID_ARG, "point %lld: segment code %d outside the polyline", (long long)i, code);
+        int32_t z0, z1;
+        segments_at(neumann->xy, nv, charges[2 * i], charges[2 * i + 1], &z0, &z1);
+        out[i] = point_visible(v, points[2 * i], points[2 * i + 1], code, charges[2 * i], charges[2 * i + 1], z0, z1,
+                               nearest) ? 1 : 0;
+    }
     return WOST_OK;
 }
 

@@ -411,9 +411,15 @@ int wost_solve_distributed(wost_handle* h, wost_comm* c, const float* points, in
     else row = 2 * ns + 1;
     if (n_points > 0 && !points) row = 0;
     RcclRun run{h, c, points, n_points, walks_per_point, max_steps, eps, seed};
-    double key[6] = {0, 0, 0, 0, 0, 0};
+    // wost_dist_solve_key's six values, then the checksum of the handle's point charges (0 when
+    // it has none): ranks whose electrodes differ must not merge their sums
+    double key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (n_points >= 0 && (points || n_points == 0)) (void)wost_dist_solve_key(seed, eps, max_steps, points, n_points, key);
-    wost_dist_ops ops{&run, rccl_prepare, rccl_solve_range, rccl_allreduce, rccl_allgather, key, 6};
+    uint64_t chk = 0;
+    if (h) (void)wost_point_sources_info(h, nullptr, &chk);
+    key[6] = (double)(uint32_t)chk;
+    key[7] = (double)(uint32_t)(chk >> 32);
+    wost_dist_ops ops{&run, rccl_prepare, rccl_solve_range, rccl_allreduce, rccl_allgather, key, 8};
     int64_t w0 = 0, w1 = 0;
     uint64_t steps = 0;
     const int rc = wost_distributed_run(&ops, c->n_ranks, c->rank, n_points, walks_per_point, row, point_stats, &w0,

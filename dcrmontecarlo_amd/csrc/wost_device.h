@@ -1971,4 +1971,158 @@ WOST_HD Hit intersect_polylines_tree(const SegTree& t, float px, float py, float
     return intersect_finish<NORMAL>(t.v, bi, best, px, py, dx, dy, qx, qy, r);
 }
 
+// ---------------------------------------------------------------------------
+// Point sources (compat="fixed"; wost_set_point_sources). The source
+// integral of a step, int G_B(x, y) f(y) dy over the star-shaped region, with
+// f = q delta(z) is q G_B(x, z) whenever z lies in the step's ball and is visible from
+// x: nothing is sampled. G_B is the Green's function of the ball B(x, R) with its pole
+// at the centre -- the kernel the sampled estimator integrates.
+// ---------------------------------------------------------------------------
+constexpr float kInv2PiF = 0.15915494309189533577f;
+
+// Laplace / Poisson / mixed: ln(R / r) / (2 pi), 0 < r < R.
+WOST_HD float ball_greens(float r, float R) { return f_log(f_div(R, r)) * kInv2PiF; }
+
+// I0(x), 0 <= x <= 3.75 (Abramowitz & Stegun 9.8.1, |error| < 1.6e-7)
+WOST_HD float bessel_i0_small(float x) {
+    const float u = x * (1.0f / 3.75f), t = u * u;
+    return 1.0f + t * (3.5156229f + t * (3.0899424f + t * (1.2067492f + t * (0.2659732f + t * (0.0360768f +
+                                                                                             t * 0.0045813f)))));
+}
+// exp(-x) I0(x), x >= 0 (9.8.1; 9.8.2 beyond 3.75: |error| < 1.9e-7 of sqrt(x) exp(-x) I0)
+WOST_HD float bessel_i0e(float x) {
+    if (x <= 3.75f) return bessel_i0_small(x) * f_exp(-x);
+    const float u = 3.75f * f_rcp(x);
+    const float p = 0.39894228f + u * (0.01328592f + u * (0.00225319f + u * (-0.00157565f + u * (0.00916281f + u * (
+                        -0.02057706f + u * (0.02635537f + u * (-0.01647633f + u * 0.00392377f)))))));
+    return p * f_rsq(x);
+}
+// K0(x) + ln(x / 2) I0(x), 0 < x <= 2 (9.8.5, |error| < 1e-8)
+WOST_HD float bessel_k0_small_poly(float x) {
+    const float h = 0.5f * x, y = h * h;
+    return -0.57721566f + y * (0.42278420f + y * (0.23069756f + y * (0.03488590f + y * (0.00262698f + y * (
+                              0.00010750f + y * 0.00000740f)))));
+}
+// exp(x) K0(x), x >= 2 (9.8.6, |error| < 1.9e-7 of sqrt(x) exp(x) K0)
+WOST_HD float bessel_k0e_large(float x) {
+    const float z = 2.0f * f_rcp(x);
+    const float p = 1.25331414f + z * (-0.07832358f + z * (0.02189568f + z * (-0.01062446f + z * (0.00587872f + z * (
+                        -0.00251540f + z * 0.00053208f)))));
+    return p * f_rsq(x);
+}
+
+// Delta tracking: [K0(t) - K0(s) I0(t) / I0(s)] / (2 pi), t = r sqrt_sb, s = R sqrt_sb,
+// 0 < r < R (0 on and outside the sphere). Three ranges, none of which forms K0(s) I0(t)
+// / I0(s) from unscaled factors (I0(s) overflows float32 at s ~ 90, K0(s) underflows):
+//  s <= 2         the two logarithms of 9.8.5 are subtracted analytically, ln(s / t) I0(t),
+//                 so s -> 0 recovers ball_greens without cancellation;
+//  t <= 2 < s     K0(t) - K0e(s) I0e(t) / I0e(s) exp(t - 2 s);
+//  2 < t          exp(-t) [K0e(t) - K0e(s) I0e(t) / I0e(s) exp(2 (t - s))].
+// The products t and s carry their rounding residuals (one fma each) into the
+// exponentials: exp(-t) would otherwise amplify the half ulp of t by t.
+WOST_HD float ball_greens_screened(float r, float R, float sqrt_sb) {
+    const float t = r * sqrt_sb, s = R * sqrt_sb;
+    if (!(t < s)) return 0.0f;
+    const float tl = fmaf(r, sqrt_sb, -t), sl = fmaf(R, sqrt_sb, -s);   // t + tl, s + sl: the exact products
+    float g;
+    if (s <= 2.0f) {
+        const float it = bessel_i0_small(t);
+        const float ratio = f_div(it, bessel_i0_small(s));
+        g = f_log(f_div(s, t)) * it + (bessel_k0_small_poly(t) - bessel_k0_small_poly(s) * ratio);
+    } else {
+        const float q = bessel_k0e_large(s) * f_div(bessel_i0e(t), bessel_i0e(s));
+        if (t <= 2.0f) {
+            const float k0t = bessel_k0_small_poly(t) - f_log(0.5f * t) * bessel_i0_small(t);
+            const float e = (t - 2.0f * s) + (tl - 2.0f * sl);
+            g = k0t - q * f_exp(e);
+        } else {
+            const float e2 = 2.0f * ((t - s) + (tl - sl));
+            g = (f_exp(-t) * (1.0f - tl)) * (bessel_k0e_large(t) - q * f_exp(e2));
+        }
+    }
+    return g * kInv2PiF;
+}
+
+// A point on the Neumann polyline in one int (the walker after a Neumann hit, a query
+// point that starts there): 0 = interior, seg + 1 = on segment seg with its left normal
+// pointing into the domain, -(seg + 1) = its right normal.
+WOST_HD int boundary_code(int seg, bool right_inward) { return right_inward ? -(seg + 1) : seg + 1; }
+
+// The ball radius of a walker ON Neumann segment seg (xcode): r, cut at the end vertices of
+// that segment where the boundary turns away from the domain (a re-entrant corner: the next
+// segment leaves on the outer side). The silhouette test sees the walker's own segment
+// edge-on (a zero cross product) and never counts its end vertices, but beyond such a
+// vertex the flat side of the half-ball is no longer boundary and the half-ball's
+// mean-value property does not hold. A closed polyline (first vertex == last) wraps.
+template <class VP>
+WOST_HD float boundary_corner_radius(VP sv, int nv, float px, float py, int xcode, float r) {
+#pragma clang fp contract(off)
+    const int s = (xcode < 0 ? -xcode : xcode) - 1;
+    const float2 a = sv[s], b = sv[s + 1];
+    float nx = -(b.y - a.y), ny = b.x - a.x;   // the inward normal, times the segment's length
+    if (xcode < 0) { nx = -nx; ny = -ny; }
+    const float2 v0 = sv[0], vl = sv[nv - 1];
+    const bool closed = v0.x == vl.x && v0.y == vl.y;
+    const int inext = s + 2 < nv ? s + 2 : (closed && nv > 3 ? 1 : -1);
+    const int iprev = s >= 1 ? s - 1 : (closed && nv > 3 ? nv - 2 : -1);
+    float r2 = r * r;
+    if (inext >= 0) {
+        const float2 c = sv[inext];
+        const float d2 = (px - b.x) * (px - b.x) + (py - b.y) * (py - b.y);
+        if ((c.x - b.x) * nx + (c.y - b.y) * ny < 0.0f && d2 < r2) r2 = d2;
+    }
+    if (iprev >= 0) {
+        const float2 c = sv[iprev];
+        const float d2 = (px - a.x) * (px - a.x) + (py - a.y) * (py - a.y);
+        if ((c.x - a.x) * nx + (c.y - a.y) * ny < 0.0f && d2 < r2) r2 = d2;
+    }
+    return r2 < r * r ? sqrtf(r2) : r;
+}
+
+// Is the charge at z visible from x (no Neumann crossing strictly between them)?
+// nearest(ox, oy, ex, ey, len): the nearest-crossing query of the kernel (the scans'
+// intersect_polylines_ray, the tree's intersect_polylines_tree<false, true>) from o
+// along e, a hit when within len. xcode: boundary_code of x. zs0, zs1: the segment(s)
+// z lies on (two at a vertex), or -1. sv: the polyline's vertices (x's segment only).
+// Survey electrodes lie ON the Neumann surface and so does the walker after a Neumann
+// hit, so the ray starts or ends on a segment or runs along one; crossings with x's
+// own and z's own segments say nothing and are passed over:
+//  1. x and z on one segment: visible (along the boundary counts as inside);
+//  2. x on a segment: z must not lie behind it (on its outer side by more than the
+//     coordinates' rounding) -- without this the two slopes of a V-shaped valley would
+//     see each other through the air, since both their segments are passed over;
+//  3. from x towards z: a miss is visible, a crossing of another segment is blocked, and
+//     a crossing of x's or z's own segment moves the origin there and asks again (a line
+//     crosses each of the at most three such segments once; four queries at the most,
+//     then blocked).
+// A ray that leaves x inwards (2.) and meets no other segment stays inside until z, so z's
+// side needs no test of its own.
+template <class VP, class Query>
+WOST_HD bool point_visible(VP sv, float px, float py, int xcode, float zx, float zy, int zs0, int zs1, Query nearest) {
+#pragma clang fp contract(off)
+    const int xs = (xcode < 0 ? -xcode : xcode) - 1;
+    if (xs >= 0 && (xs == zs0 || xs == zs1)) return true;
+    const float scale = 9.5367431640625e-07f * ((fabsf(px) + fabsf(py)) + (fabsf(zx) + fabsf(zy)));   // 2^-20 |.|_1
+    if (xs >= 0) {
+        const float2 a = sv[xs], b = sv[xs + 1];
+        const float ux = b.x - a.x, uy = b.y - a.y;
+        float side = ux * (zy - py) - uy * (zx - px);   // (z - x) . left normal, times |u|
+        if (xcode < 0) side = -side;
+        if (side < -(scale * (fabsf(ux) + fabsf(uy)))) return false;
+    }
+    float ox = px, oy = py;
+#pragma unroll 1
+    for (int it = 0; it < 4; ++it) {
+        const float ex = zx - ox, ey = zy - oy;
+        const float len = sqrtf(ex * ex + ey * ey);
+        if (!(len > scale)) return true;
+        const Hit h = nearest(ox, oy, ex, ey, len);
+        if (!h.hit) return true;
+        if (h.seg != xs && h.seg != zs0 && h.seg != zs1) return false;
+        ox = h.x;
+        oy = h.y;
+    }
+    return false;
+}
+
 }  // namespace wost

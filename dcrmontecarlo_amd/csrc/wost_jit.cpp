@@ -710,7 +710,7 @@ bool jit_fused_neumann_scan(const Options& o, int mode, int nn) {
 std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, const DTerm* terms, const DFactor* factors,
                          const float* dverts, int nd, const float* nverts, int nn, bool record, int n_sources,
                          int block, const float* seg_phi, bool global_polylines, int tree_stage,
-                         bool exact_trig, int n_wavenumbers) {
+                         bool exact_trig, int n_wavenumbers, int n_charges) {
     const bool neu = mode_neu(mode);
     const bool src = mode_src(mode);
     const bool delta = mode_delta(mode);
@@ -908,7 +908,9 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
       << (delta ? "true" : "false") << ", " << (tree ? "true" : "false") << ", " << (record ? "true" : "false")
       << ", " << n_sources << ", " << (mode_fix(mode) ? "true" : "false") << ", "
       << (global_polylines ? "true" : "false");
-    if (n_wavenumbers >= 1) o << ", " << n_wavenumbers;   // NK (a handle without wavenumbers: its kernel as ever)
+    // NK (a handle without wavenumbers: its kernel as ever), then PC (likewise without point charges)
+    if (n_wavenumbers >= 1 || n_charges >= 1) o << ", " << std::max(n_wavenumbers, 1);
+    if (n_charges >= 1) o << ", " << n_charges;
     o << ">(A, fld, smem);\n}\n";
     if (delta)   // alpha at the query points, with these fields (WalkArgs::point_alpha)
         o << "extern \"C\" __global__ void __launch_bounds__(256)\n"

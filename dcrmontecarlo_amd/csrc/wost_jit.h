@@ -45,11 +45,13 @@ bool jit_fused_neumann_scan(const Options& o, int mode, int nn);
 // `opt`: the handle's kernel options (wost_options.h).
 // n_wavenumbers >= 1 (wost_set_wavenumbers): the walk carries that many attenuations and
 // reads their k^2 from WalkArgs::k2 at run time (wost_walk.h NK); 0: none set.
+// n_charges >= 1 (wost_set_point_sources): the walk scores that many point charges, read
+// from WalkArgs::charges at run time (wost_walk.h PC); 0: none set, the source as ever.
 std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, const DTerm* terms, const DFactor* factors,
                          const float* dverts, int nd, const float* nverts, int nn, bool record,
                          int n_sources = 1, int block = 256, const float* seg_phi = nullptr,
                          bool global_polylines = false, int tree_stage = 0, bool exact_trig = true,
-                         int n_wavenumbers = 0);
+                         int n_wavenumbers = 0, int n_charges = 0);
 
 // Compiles (or fetches from the caches) the source for `device` and returns
 // the kernel. On failure returns false and a message in *err.

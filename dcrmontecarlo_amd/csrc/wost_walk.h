@@ -102,7 +102,39 @@ struct WalkArgs {
     // loads), so one kernel per (problem, NS, NK) serves every wavenumber set; all 0 when none
     // is set, and only kernels built with WOST_WAVENUMBERS read it.
     float k2[WOST_MAX_SOURCES];
+    // point sources (wost_set_point_sources; read only by kernels built with a charge count
+    // PC > 0): kChargeWords words, arrays of WOST_MAX_POINT_CHARGES entries each (ChargeWord).
+    // Read at run time (wave-uniform scalar loads), so one kernel per (problem, PC, NS, NK)
+    // serves every electrode set.
+    const float* charges;
+    // ... and boundary_code (wost_device.h) of each query point: a walk that starts on the
+    // Neumann polyline starts as a walk that has just hit it there (PC > 0 kernels only)
+    const int32_t* point_code;
 };
+
+// Offsets of the per-charge arrays in WalkArgs::charges: position (x, y interleaved),
+// strength, alpha at the charge (delta tracking: point_alpha_body's bits), and as ints the
+// source channel and the Neumann segment(s) the charge lies on (-1: none; two at a vertex).
+enum ChargeWord : int {
+    CHG_XY = 0,
+    CHG_Q = 2 * WOST_MAX_POINT_CHARGES,
+    CHG_ALPHA = 3 * WOST_MAX_POINT_CHARGES,
+    CHG_SOURCE = 4 * WOST_MAX_POINT_CHARGES,
+    CHG_SEG0 = 5 * WOST_MAX_POINT_CHARGES,
+    CHG_SEG1 = 6 * WOST_MAX_POINT_CHARGES
+};
+constexpr int kChargeWords = 7 * WOST_MAX_POINT_CHARGES;
+// word i of the charge buffer, as a scalar load from constant memory
+__device__ __forceinline__ float charge_float(const float* c, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return ((const __attribute__((address_space(4))) float*)c)[i];
+#else
+    return c[i];
+#endif
+}
+__device__ __forceinline__ int charge_int(const float* c, int i) {
+    return __builtin_bit_cast(int, charge_float(c, i));
+}
 
 // The refill's id arithmetic: local walk `lid` of the launch `A` -> its global walk id `wid`
 // and its point index `pid` (uint64_t lvalues). Integer quotients without a 64-bit division:
@@ -798,6 +830,14 @@ __device__ __forceinline__ Hit intersect_polylines_tree_wave(const SegTree& t, f
 // precompiled ones, NK = 1, and the specialised ones of a handle with wavenumbers set); the
 // others compile the add out, so a handle without wavenumbers runs the kernel it always ran.
 // NK > 1 tree kernels run without walk pools (a parked walk holds one w).
+// PC > 0 (point sources, FIX only): the handle's source is PC point charges
+// q_p delta(z_p), charge p belonging to source channel s(p) (A.charges, run-time data). A
+// step scores each charge inside its ball and visible from x with q_p G_B(x, z_p)
+// (ball_greens / ball_greens_screened, point_visible) instead of sampling a point y and
+// evaluating f(y); under delta tracking the sample still drives the collision, without
+// it nothing is sampled. A query point on the Neumann polyline starts as a walk that has
+// just hit it there (A.point_code). No walk pools (a parked walk holds no xcode). Kernels
+// with PC == 0 compile none of this: their code is what it was.
 #ifndef WOST_WAVENUMBERS
 #define WOST_WAVENUMBERS 0
 #endif
@@ -909,7 +949,7 @@ __device__ __forceinline__ void walk_sincos(float theta, float& sn, float& cs, b
 #define WOST_PIN_U4(u) ((void)0)
 #endif
 template <bool NEU, bool SRC, bool DELTA, bool TREE, bool REC, int NS = 1, bool FIX = false, bool GL = false,
-          int NK = 1, class F>
+          int NK = 1, int PC = 0, class F>
 __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsigned char* smem) {
     // the walk's position updates round op by op like the reference (torch CPU
     // has no FMA contraction); the field math it calls keeps its own setting
@@ -917,6 +957,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     static_assert(NS >= 1 && (NS == 1 || SRC) && (NS == 1 || !REC), "multi-source walks need a source, no recorder");
     static_assert(NK >= 1 && (NK == 1 || (DELTA && !REC && WOST_WAVENUMBERS)) && NK * NS <= WOST_MAX_SOURCES,
                   "wavenumber channels need delta tracking, no recorder, at most WOST_MAX_SOURCES channels");
+    static_assert(PC >= 0 && PC <= WOST_MAX_POINT_CHARGES && (PC == 0 || (FIX && SRC && !REC)),
+                  "point sources need compat=\"fixed\", a source mode, no recorder, at most WOST_MAX_POINT_CHARGES charges");
     constexpr int NC = NK * NS;   // channels: c = j * NS + s
     constexpr bool kStageD = !F::kConstDirichlet && !GL;
     // the Neumann polyline is staged also when compiled in (FIX scans sN itself; a few
@@ -967,7 +1009,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         for (int i = threadIdx.x; i < kGnormCells; i += blockDim.x) sG[i] = g[i];
     }
     // this workgroup's walk pools (header: lock, walks parked near, walks parked far)
-    uint32_t* const pool = (TREE && WOST_TREE_POOL && NK == 1 && A.pool != nullptr)
+    uint32_t* const pool = (TREE && WOST_TREE_POOL && NK == 1 && PC == 0 && A.pool != nullptr)
                                ? A.pool + (size_t)blockIdx.x * (size_t)A.pool_wg_words : nullptr;
     if (pool != nullptr && threadIdx.x < 4) pool[threadIdx.x] = 0u;
     __syncthreads();
@@ -1018,6 +1060,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     int k = 0;                  // step_count
     bool onB = false;           // onBoundary
     float phi = 0.f;            // atan2 of currentNormal (:228), set when onB
+    int xcode = 0;              // (PC > 0) boundary_code of the current point: its segment and inward side
     float w[NK];                // attenuation_coef (one per wavenumber)
 #pragma unroll
     for (int j = 0; j < NK; ++j) w[j] = 1.f;
@@ -1189,6 +1232,15 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 const float2 q = A.points[pid];
                 px = q.x; py = q.y;
                 k = 0; dD = FIX ? WOST_INF : 1.0f; onB = false; phi = 0.f;
+                if constexpr (PC > 0 && NEU) {   // a query point on the Neumann polyline: as after a hit there
+                    xcode = A.point_code[pid];
+                    if (xcode != 0) {
+                        const int sg = (xcode < 0 ? -xcode : xcode) - 1;
+                        onB = true;
+                        phi = TREE ? A.seg_phi[sg] : fld.neumann_phi(phiP, sg);
+                        if (xcode < 0) phi = phi + kPiF;
+                    }
+                }
 #pragma unroll
                 for (int j = 0; j < NK; ++j) w[j] = 1.f;
 #pragma unroll
@@ -1335,6 +1387,12 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         } else {
             r = dd > A.rmin ? dd : A.rmin;                           // :215
         }
+        if constexpr (PC > 0 && NEU) {   // a walker on a Neumann segment: its half-ball ends at a re-entrant corner
+            if (onB) {
+                const float rc = boundary_corner_radius(TREE ? A.nverts : nP, A.nn, px, py, xcode, r);
+                r = rc > A.rmin ? rc : A.rmin;
+            }
+        }
         WOST_PHASE("philox_direction");
         if (!kFused) draw_direction();
 #if !defined(WOST_ABL_NO_PHILOX)
@@ -1348,6 +1406,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
 #endif
 
         float xnx, xny;
+        const int xcode0 = xcode;                                    // the current point's, like onB0
         WOST_PHASE("ray_query");
         if (NEU) {                                                   // :235-236
 #if defined(WOST_ABL_NO_RAY)
@@ -1374,7 +1433,11 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 // its left side, i.e. cross(d, u) > 0 (then dot(left normal, d) < 0)
                 const float2* const sv = TREE ? A.nverts : nP;   // the tree kernels stage none
                 const float2 a = sv[h.seg], b = sv[h.seg + 1];
-                if (!(cs * (b.y - a.y) - sn * (b.x - a.x) > 0.0f)) phi = phi + kPiF;
+                const bool right_inward = !(cs * (b.y - a.y) - sn * (b.x - a.x) > 0.0f);
+                if (right_inward) phi = phi + kPiF;
+                if constexpr (PC > 0) xcode = boundary_code(h.seg, right_inward);
+            } else if constexpr (PC > 0) {
+                xcode = 0;
             }
         } else {                                                     // :238-239
             xnx = px + r * cs;
@@ -1391,10 +1454,13 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             float rs;
             if constexpr (FIX && DELTA)                              // Q4/Q5 fixed: this ball's law
                 rs = sample_rho_screened_fixed(A.table + kFixTableOffset, u01(rn.y), r * sqrt_sb) * r;
-            else
+            else if constexpr (PC == 0)                              // (point sources: nothing is sampled)
                 rs = sample_rho_tail(sT, node0, u01(rn.y)) * r;      // :244 (sampler, quirks Q3-Q5)
             if (WOST_ABL_DUP & 16) rs = dup_merge(rs, sample_rho_tail(sT, node0, u01(rn.y | dup_zero())) * r);
-            if constexpr (FIX && !DELTA) {                           // Q13 fixed: own direction
+            if constexpr (FIX && !DELTA && PC > 0) {
+                // point sources without delta tracking: the charges are scored below, exactly;
+                // no source sample, no direction of its own, no visibility query for it
+            } else if constexpr (FIX && !DELTA) {                    // Q13 fixed: own direction
                 float ts = (u01(rn.w) * 2.0f) * kPiF;
                 if (NEU && onB0) ts = ts / 2.0f + (phi0 - kPiF / 2.0f);   // the inward hemisphere
                 float cs2, sn2;
@@ -1439,7 +1505,67 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 }
             }
             WOST_PHASE("source_contribution");
-            if constexpr (NC == 1) {
+            if constexpr (PC > 0) {
+                // Point sources: every charge inside the step's ball and visible from x scores
+                // q G_B(x, z), the sampled estimator's f G_norm with the sample integrated out
+                // (under delta tracking its rsq(alpha(y) alpha(x)) at y = z). On a Neumann
+                // boundary point the star-shaped region is a half-ball, whose Green's function
+                // at a boundary pole is twice the ball's: the factor 2 of the sampled estimator.
+                // The in-ball test is per lane; visibility and the Bessel evaluation run only
+                // when a lane of the wave needs them. The per-source sums are formed first, in
+                // charge order, so that a source's value does not depend on the other sources.
+                float cq[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) cq[s] = 0.0f;
+                const float r2 = r * r;
+                auto nearest = [&](float ox, float oy, float ex, float ey, float len) {
+                    if constexpr (TREE) return intersect_polylines_tree<false, true>(tree, ox, oy, ex, ey, len);
+                    else return fld.neumann_intersect_nearest(nP, A.nn, ox, oy, ex, ey, len);
+                };
+#pragma unroll 1
+                for (int p = 0; p < PC; ++p) {
+                    const float zx = charge_float(A.charges, CHG_XY + 2 * p);
+                    const float zy = charge_float(A.charges, CHG_XY + 2 * p + 1);
+                    const float ex = zx - px, ey = zy - py;
+                    const float d2 = ex * ex + ey * ey;
+                    // (delta tracking: beyond t = r_p sqrt(sigma_bar) = 88 the function is below
+                    // float32's smallest normal, exp(-88) = 6e-39: such a charge scores nothing)
+                    const bool in = d2 < r2 && (!DELTA || d2 * sigma_bar < 7744.0f);
+                    if (WOST_ANY(in)) {
+                        WOST_NO_SPECULATION();
+                        if (in) {
+                            bool vis = true;
+                            if constexpr (NEU)
+                                vis = point_visible(TREE ? A.nverts : nP, px, py, xcode0, zx, zy,
+                                                    charge_int(A.charges, CHG_SEG0 + p),
+                                                    charge_int(A.charges, CHG_SEG1 + p), nearest);
+                            if (vis) {
+                                // r_p clamped at rmin: the potential of an electrode of radius eps / 2
+                                // (a query point that is itself a charge stays finite)
+                                float rp = f_sqrt(d2);
+                                rp = rp > A.rmin ? rp : A.rmin;
+                                const float q = charge_float(A.charges, CHG_Q + p);
+                                float v;
+                                if constexpr (DELTA)
+                                    v = (q * ball_greens_screened(rp, r, sqrt_sb)) *
+                                        f_rsq(charge_float(A.charges, CHG_ALPHA + p) * ax);
+                                else
+                                    v = q * ball_greens(rp, r);
+                                const int sp = charge_int(A.charges, CHG_SOURCE + p);
+#pragma unroll
+                                for (int s = 0; s < NS; ++s) cq[s] = sp == s ? cq[s] + v : cq[s];
+                            }
+                        }
+                    }
+                }
+                const float bf = (NEU && onB0) ? 2.0f : 1.0f;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const float c = cq[s] * bf;
+#pragma unroll
+                    for (int j = 0; j < NK; ++j) total[j * NS + s] = total[j * NS + s] + (DELTA ? c * w[j] : c);
+                }
+            } else if constexpr (NC == 1) {
                 float c = 0.0f;
                 if (!clipped) {
                     float f = fld.f(yx, yy);
@@ -1507,6 +1633,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             px = collide ? yx : xnx;
             py = collide ? yy : xny;
             onB = collide ? false : onB;                             // a collision point is interior
+            if constexpr (PC > 0) xcode = collide ? 0 : xcode;
             ax = anew;
         } else if (DELTA) {                                          // :271-284
             const float mu = u01(rn.z);

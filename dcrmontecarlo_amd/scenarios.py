@@ -49,6 +49,16 @@ class Scenario:
                              PolyLinesSimple(self.neumann) if self.neumann is not None else None,
                              source=self.f, sigma=self.sigma, alpha=self.alpha, **kw)
 
+    def kernel_source_points(self, n_charges: int, n_sources: int = 1, **kw) -> str:
+        """Generated source of the walk kernel that scores ``n_charges`` point charges in
+        ``n_sources`` sources instead of this scenario's source field (host only)."""
+        from .geometry import PolyLinesSimple
+        from .solvers.WoStSolver import kernel_source_points
+
+        return kernel_source_points(PolyLinesSimple(self.dirichlet), self.g,
+                                    PolyLinesSimple(self.neumann) if self.neumann is not None else None,
+                                    sigma=self.sigma, alpha=self.alpha, n_charges=n_charges, n_sources=n_sources, **kw)
+
 
 def torch_linspace(start: float, end: float, steps: int) -> np.ndarray:
     """torch.linspace in float32 (ATen CPU: first half from start, second half from end)."""

@@ -137,6 +137,64 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
     return buf.value.decode()
 
 
+def kernel_source_points(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoundary=None, sigma=None,
+                         alpha=None, *, n_charges: int, n_sources: int = 1, n_wavenumbers: int = 0,
+                         sigma_bar: float | None = None, compat: str = "fixed") -> str:
+    """HIP source of the walk kernel of a solver with ``n_charges`` point charges in
+    ``n_sources`` source channels (set_point_sources; wost_kernel_source_points, no device
+    needed). It depends on the counts only: positions and strengths are run-time data."""
+    dxy = np.asarray(_np(dirichletBoundary.points), dtype=np.float32).reshape(-1, 2)
+    nxy = None if neumannBoundary is None else np.asarray(_np(neumannBoundary.points), dtype=np.float32).reshape(-1, 2)
+    conv = _Converter(_bounds_of(dxy, nxy))
+    g = conv(dirichletBoundaryFunction, "dirichletBoundaryFunction")
+    s = conv(sigma, "sigma")
+    a = conv(alpha, "alpha", is_alpha=True)
+    if a is not None and a.is_constant():
+        a = detach(a)
+    if compat not in _lib.COMPAT:
+        raise ValueError(f"compat must be one of {sorted(_lib.COMPAT)}")
+    prob, keep = _problem(dxy, nxy, g, None, s, a, compat, 0, sigma_bar)
+    n = ctypes.c_int64(0)
+    call = lambda buf, cap: _lib.lib.wost_kernel_source_points(ctypes.byref(prob), int(n_charges), int(n_sources),
+                                                                int(n_wavenumbers), buf, cap, ctypes.byref(n))
+    _lib.check(call(None, 0), "wost_kernel_source_points")
+    buf = ctypes.create_string_buffer(n.value + 1)
+    _lib.check(call(buf, n.value + 1), "wost_kernel_source_points")
+    return buf.value.decode()
+
+
+def pack_point_charges(charges):
+    """``charges``: a list of sources, each a list of ``(position, strength)`` pairs or an
+    object with such a ``.charges`` list (survey.point_electrode / point_dipole) -> (ctypes
+    array of wost_point_charge, n, n_sources). Raises ValueError for what
+    wost_set_point_sources would refuse: more than WOST_MAX_POINT_CHARGES charges, a source
+    without a charge, a non-finite position or strength."""
+    rows = []
+    srcs = list(charges)
+    if not srcs:
+        raise ValueError("point sources: need at least one source (None clears them)")
+    for s, src in enumerate(srcs):
+        lst = list(getattr(src, "charges", src))
+        if not lst:
+            raise ValueError(f"point sources: source {s} has no charge")
+        for pos, q in lst:
+            x, y = (float(v) for v in np.asarray(_np(pos), np.float64).ravel()[:2])
+            if not (np.isfinite(x) and np.isfinite(y) and abs(float(q)) <= 3.4028234663852886e38):   # (finite as float32)
+                raise ValueError(f"point sources: source {s} has a non-finite position or strength")
+            rows.append((x, y, float(q), s))
+    if len(rows) > _lib.WOST_MAX_POINT_CHARGES:
+        raise ValueError(f"point sources: {len(rows)} charges exceed {_lib.WOST_MAX_POINT_CHARGES} per launch")
+    arr = (_lib.WostPointCharge * len(rows))()
+    for i, (x, y, q, s) in enumerate(rows):
+        arr[i].x, arr[i].y, arr[i].strength, arr[i].source = x, y, q, s
+    return arr, len(rows), len(srcs)
+
+
+def is_point_source(src) -> bool:
+    """A survey.PointSource-like source (an object with a ``charges`` list)."""
+    return hasattr(src, "charges")
+
+
 class _Converter:
     """Coefficient arguments -> device fields: Fields and numbers as they are,
     Python callables traced into closed form or tabulated over the domain
@@ -211,6 +269,7 @@ class WostSolver_2D:
         self.last_timing = None
         self.last_point_sums = None   # (sum, sum^2, steps) per point of the last solve
         self.wavenumbers = None       # set_wavenumbers: the k of the handle's channels, or None
+        self.point_sources = None     # set_point_sources: the sources' charge lists, or None
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -508,6 +567,102 @@ class WostSolver_2D:
 
 
 
+    # ---- point sources (include/wost.h wost_set_point_sources) ----------------
+    def set_point_sources(self, charges=None):
+        """Score point charges instead of a source field (compat="fixed" only, a solver built
+        without ``source``). ``charges``: a list of sources, each a list of
+        ``(position, strength)`` -- the strength is the current that enters the 2-D domain --
+        or of survey.point_electrode / point_dipole objects; ``None`` clears them. A walk
+        scores every charge inside a step's ball and visible from its point exactly, with the
+        ball's Green's function: no width, no sampling. ``solve`` / ``solve_walks`` (one
+        source), ``solve_point_sources[_walks]``, ``solve_range`` and ``solve_wavenumbers``
+        then score them; at most WOST_MAX_POINT_CHARGES charges and WOST_MAX_SOURCES channels
+        (sources x wavenumbers) per launch. Positions are data, not code: one compiled kernel
+        per (problem, charge count, source count, wavenumber count) serves every electrode set."""
+        if charges is None:
+            _lib.check(_lib.lib.wost_set_point_sources(self._h, None, 0, 0), "WostSolver_2D.set_point_sources")
+            self.point_sources = None
+            return
+        arr, n, n_src = pack_point_charges(charges)
+        _lib.check(_lib.lib.wost_set_point_sources(self._h, arr, n, n_src), "WostSolver_2D.set_point_sources")
+        self.point_sources = [list(getattr(s, "charges", s)) for s in charges]
+
+    def _point_source_chunks(self, sources, n_k: int = 1):
+        """Runs of sources that fit one launch: at most WOST_MAX_POINT_CHARGES charges and
+        WOST_MAX_SOURCES // n_k sources."""
+        lists = [list(getattr(s, "charges", s)) for s in sources]
+        s_max = max(1, _lib.WOST_MAX_SOURCES // max(1, n_k))
+        chunks, cur, cnt = [], [], 0
+        for lst in lists:
+            if len(lst) > _lib.WOST_MAX_POINT_CHARGES:
+                raise ValueError(f"a point source of {len(lst)} charges exceeds {_lib.WOST_MAX_POINT_CHARGES} per launch")
+            if cur and (cnt + len(lst) > _lib.WOST_MAX_POINT_CHARGES or len(cur) >= s_max):
+                chunks.append(cur)
+                cur, cnt = [], 0
+            cur.append(lst)
+            cnt += len(lst)
+        if cur:
+            chunks.append(cur)
+        return chunks
+
+    @contextlib.contextmanager
+    def point_sources_installed(self, sources):
+        """The point sources ``sources`` (one launch's worth) inside the block; the solver's
+        own point sources (or none) are restored afterwards."""
+        saved = self.point_sources
+        self.set_point_sources(sources)
+        try:
+            yield len(sources)
+        finally:
+            self.set_point_sources(saved)
+
+    def _solve_point_sources(self, solvePoints, sources, nWalks, maxSteps, eps, seed, want_walks):
+        p = _points_np(solvePoints)
+        n = p.shape[0]
+        nWalks = int(nWalks)
+        if nWalks < 1:
+            raise ValueError("nWalks must be >= 1")
+        nb = self.num_blocks(n, nWalks)
+        sums, vals, steps = [], [], None
+        for chunk in self._point_source_chunks(sources, 1 if self.wavenumbers is None else len(self.wavenumbers)):
+            with self.point_sources_installed(chunk) as S:
+                if self.num_channels() != S:
+                    raise ValueError("solve_point_sources scores one value per source, but the solver has wavenumbers "
+                                     "set: use solve_wavenumbers(points, k, sources=...)")
+                s = np.zeros((n, 2 * S + 1), np.float64)
+                wv = np.empty(n * nWalks * S, np.float32) if want_walks else None
+                ws = np.empty(n * nWalks, np.uint32) if want_walks else None
+                _lib.check(_lib.lib.wost_solve_multi(self._h, _lib.fptr(p), n, nWalks, 0, nb, int(maxSteps),
+                                                     float(eps), int(seed) & (2**64 - 1), None, _lib.dptr(s),
+                                                     _lib.fptr(wv), _lib.u32ptr(ws)), "WostSolver_2D.solve_point_sources")
+                self.last_timing = self.timing()
+            sums.append(s)
+            if want_walks:
+                vals.append(wv.reshape(n, nWalks, S).transpose(2, 0, 1))
+                steps = ws.reshape(n, nWalks)
+        return sums, vals, steps
+
+    def solve_point_sources(self, solvePoints, sources, nWalks=1000, maxSteps=1000, eps=1e-4, *, seed: int = 0,
+                            return_stats: bool = False):
+        """solve_sources for point sources: u[k] is the solve with the charges of
+        ``sources[k]`` alone, all scored by the same walks, bit for bit. Returns float32
+        [S, N]; with ``return_stats`` also a SolveStats whose mean and stderr are [S, N]."""
+        sums, _, _ = self._solve_point_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, False)
+        stats = [st for s in sums for st in _stats_of_multi(s, int(nWalks))]
+        u = np.stack([st.mean.astype(np.float32) for st in stats])
+        if not return_stats:
+            return u
+        t = self.last_timing
+        return u, SolveStats(mean=np.stack([st.mean for st in stats]), stderr=np.stack([st.stderr for st in stats]),
+                             mean_steps=stats[0].mean_steps, walks=stats[0].walks, total_steps=stats[0].total_steps,
+                             kernel_ms=t["walk_kernel_ms"], total_ms=t["total_ms"])
+
+    def solve_point_sources_walks(self, solvePoints, sources, nWalks=1000, maxSteps=1000, eps=1e-4, *, seed: int = 0):
+        """Per-walk values of every point source, float32 [S, N, nWalks], and the walks' step
+        counts, uint32 [N, nWalks]."""
+        _, vals, steps = self._solve_point_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, True)
+        return np.concatenate(vals, axis=0), steps
+
     # ---- 2.5-D wavenumber batching (DESIGN.md, include/wost.h wost_set_wavenumbers) ---------
     def set_wavenumbers(self, k=None):
         """Score the screened problems div(alpha grad u) - k^2 alpha u = -f of the
@@ -542,12 +697,23 @@ class WostSolver_2D:
         kk = np.atleast_1d(np.asarray(k, np.float64)).ravel()
         if kk.size < 1:
             raise ValueError("k must hold at least one wavenumber")
-        fields = None if sources is None else self.source_fields(sources)
-        S = 1 if fields is None else len(fields)
+        points = sources is not None and len(sources) > 0 and all(is_point_source(s) or isinstance(s, (list, tuple))
+                                                                 for s in sources)
+        if sources is not None and not points and any(is_point_source(s) for s in sources):
+            raise ValueError("sources mixes point sources and fields: one kind per solve")
+        fields = None if sources is None or points else self.source_fields(sources)
+        S = 1 if sources is None else len(sources)
         K = kk.size
         nb = self.num_blocks(n, nWalks)
         s_chunk = min(S, _lib.WOST_MAX_SOURCES)
         k_chunk = max(1, _lib.WOST_MAX_SOURCES // s_chunk)
+        if points:   # source runs of at most WOST_MAX_POINT_CHARGES charges, then as many wavenumbers as fit
+            runs, s0 = [], 0
+            for chunk in self._point_source_chunks(sources, 1):
+                runs.append((s0, s0 + len(chunk), chunk))
+                s0 += len(chunk)
+        else:
+            runs = [(s0, min(S, s0 + s_chunk), None) for s0 in range(0, S, s_chunk)]
         sums = np.zeros((K, S, n, 3), np.float64)
         vals = np.empty((K, S, n, nWalks), np.float32) if want_walks else None
         steps = None
@@ -555,9 +721,11 @@ class WostSolver_2D:
         saved = self.wavenumbers
         self.set_wavenumbers(None)   # (wost_set_sources checks sources x wavenumbers)
         try:
-            for s0 in range(0, S, s_chunk):
-                s1 = min(S, s0 + s_chunk)
-                ctx = contextlib.nullcontext() if fields is None else self.sources_installed(fields[s0:s1])
+            for s0, s1, chunk in runs:
+                ctx = (self.point_sources_installed(chunk) if points else contextlib.nullcontext() if fields is None
+                       else self.sources_installed(fields[s0:s1]))
+                if points:
+                    k_chunk = max(1, _lib.WOST_MAX_SOURCES // (s1 - s0))
                 with ctx:
                     try:
                         for k0 in range(0, K, k_chunk):

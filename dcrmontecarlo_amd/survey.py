@@ -61,6 +61,38 @@ def dipole_source(a, b, width: float, current: float = 1.0) -> F.Field:
 
 
 @dataclass
+class PointSource:
+    """A source made of point charges (WostSolver_2D.set_point_sources): ``charges`` is a list
+    of ``((x, y), strength)``, the strength being the current that enters the 2-D domain."""
+
+    charges: list
+
+    def __neg__(self):
+        return PointSource([(p, -q) for p, q in self.charges])
+
+    def __add__(self, other):
+        return PointSource(list(self.charges) + list(other.charges))
+
+    def __sub__(self, other):
+        return self + (-other)
+
+
+def point_electrode(position, current: float = 1.0, surface: bool = True) -> PointSource:
+    """Current injection at a point. ``surface=True``: an electrode on the Neumann surface,
+    strength ``current / 2`` -- the half-line transform's (I / 2) delta of the 2.5-D layer
+    (wavenumber.py), and the width -> 0 limit of ``electrode_source``, whose whole-plane
+    integral is I with half of it inside the domain. ``surface=False``: ``current`` enters
+    the domain whole (an interior charge, or a 2-D line electrode on the surface)."""
+    q = 0.5 * float(current) if surface else float(current)
+    return PointSource([((float(position[0]), float(position[1])), q)])
+
+
+def point_dipole(a, b, current: float = 1.0, surface: bool = True) -> PointSource:
+    """+current at electrode position a, -current at b, as point electrodes."""
+    return point_electrode(a, current, surface) - point_electrode(b, current, surface)
+
+
+@dataclass
 class DipoleData:
     dv: np.ndarray      # [P] potential differences u(M) - u(N)
     se: np.ndarray      # [P] their Monte-Carlo standard errors (walks of M and N are independent)

@@ -33,7 +33,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .scenarios import Scenario, torch_linspace
-from .survey import (dipole_dipole_quadripoles, dipole_source, group_seed, wenner_quadripoles)
+from .survey import (dipole_dipole_quadripoles, dipole_source, group_seed, point_dipole, wenner_quadripoles)
 
 
 # ---------------------------------------------------------------------------
@@ -136,7 +136,8 @@ def wavenumber_groups(k, groups: int = 1):
 
 def transformed_potentials(solvers, groups, points, sources, k, w, n_walks: int, max_steps: int, eps: float,
                            seed: int = 0) -> Transformed:
-    """sum_j w_j u_{k_j} of every source at every point. ``groups``: index arrays into k,
+    """sum_j w_j u_{k_j} of every source (fields, or point sources: survey.point_electrode /
+    point_dipole, one kind per call) at every point. ``groups``: index arrays into k,
     group g solved by ``solvers[g]`` (wavenumber_groups). Within a group all channels share
     their walks, so the standard error comes from the per-walk weighted sums
     v = sum_j w_j v_j, never from the channels' own errors (they are correlated); groups
@@ -191,10 +192,14 @@ class Survey25DResult:
     kernel_ms: float
 
 
-def _solvers_25d(sc: Scenario, k, groups, compat, device, solvers):
+def _solvers_25d(sc: Scenario, k, groups, compat, device, solvers, electrodes="gaussian"):
     idx = wavenumber_groups(k, groups) if isinstance(groups, int) else [np.asarray(g, np.int64) for g in groups]
     if solvers is None:
         kw = {} if device is None else {"device": device}
+        if electrodes == "point":   # a point-source solver has no source field
+            import dataclasses
+
+            sc = dataclasses.replace(sc, f=None)
         probe = sc.solver(compat=compat, **kw)
         solvers = [sc.solver(compat=compat, sigma_bar=sigma_bar_for(probe, float(np.max(k[g]))), **kw) for g in idx]
     if len(solvers) != len(idx):
@@ -203,7 +208,9 @@ def _solvers_25d(sc: Scenario, k, groups, compat, device, solvers):
 
 
 def _run_25d(sc, quad, tx_cols, dv_of, factor, n_walks, width, n_k, groups, seed, device, compat, solvers,
-             r_min, r_max):
+             r_min, r_max, electrodes="gaussian"):
+    if electrodes not in ("gaussian", "point"):
+        raise ValueError(f'electrodes must be "gaussian" or "point", got {electrodes!r}')
     E = len(sc.points)
     x = np.asarray(sc.points, np.float64)
     if not len(quad):
@@ -211,9 +218,12 @@ def _run_25d(sc, quad, tx_cols, dv_of, factor, n_walks, width, n_k, groups, seed
     if n_k is None:   # as many wavenumbers as the range of distances supports (wavenumber_quadrature)
         n_k = 4 if r_max <= 3.0 * r_min else 6 if r_max <= 12.0 * r_min else 8
     k, w = wavenumber_quadrature(r_min, r_max, n_k)
-    solvers, idx = _solvers_25d(sc, k, groups, compat, device, solvers)
+    solvers, idx = _solvers_25d(sc, k, groups, compat, device, solvers, electrodes)
     tx = np.unique(quad[:, tx_cols], axis=0)
-    srcs = [dipole_source(x[a], x[b], width) for a, b in tx]
+    if electrodes == "point":   # (I / 2) delta at each electrode: no width
+        srcs = [point_dipole(x[a], x[b]) for a, b in tx]
+    else:
+        srcs = [dipole_source(x[a], x[b], width) for a, b in tx]
     tr = transformed_potentials(solvers, idx, sc.points, srcs, k, w, n_walks, sc.max_steps, sc.eps, seed)
     row = {(int(a), int(b)): i for i, (a, b) in enumerate(tx)}
     t = np.array([row[(int(q[tx_cols[0]]), int(q[tx_cols[1]]))] for q in quad], np.int64)
@@ -228,7 +238,7 @@ def _run_25d(sc, quad, tx_cols, dv_of, factor, n_walks, width, n_k, groups, seed
 
 def run_wenner_survey_25d(sc: Scenario, n_walks: int, a: int = 1, width: float = 0.5, n_k: int | None = None,
                           groups=1, seed: int = 0, device: int | None = None, compat: str = "fixed",
-                          solvers=None) -> Survey25DResult:
+                          solvers=None, electrodes: str = "gaussian") -> Survey25DResult:
     """2.5-D Wenner-alpha survey of ``sc`` (its points are the surface electrodes, equally
     spaced; its alpha the conductivity): apparent resistivity of point electrodes,
     rho_a = 2 pi a dV / I with dV = V_M - V_N for the transmitter A+ / B-. Sources x
@@ -239,21 +249,25 @@ def run_wenner_survey_25d(sc: Scenario, n_walks: int, a: int = 1, width: float =
     homogeneous background solve is needed: the geometric factor is the point electrode's.
     compat: "fixed" by default -- the reference estimator's quirks bias screened solves by
     factors, and these numbers are meant to be compared with field data; its
-    walks need ~d^2 sigma_bar / 4 steps from Dirichlet distance d (set sc.max_steps)."""
+    walks need ~d^2 sigma_bar / 4 steps from Dirichlet distance d (set sc.max_steps).
+    electrodes: "gaussian" (default) injects through Gaussians of standard deviation ``width``;
+    "point" through point electrodes scored exactly (compat="fixed" only; ``width`` is
+    ignored, and ``sc`` must have no source field: its solvers are built without one)."""
     quad = wenner_quadripoles(len(sc.points), a)
     x = np.asarray(sc.points, np.float64)
     dx = float(np.linalg.norm(x[1] - x[0])) if len(x) > 1 else 1.0
     return _run_25d(sc, quad, [0, 3], lambda q: (q[:, 1], q[:, 2]),
                     lambda q, xy: np.full(len(q), wenner_geometric_factor(a * dx)), n_walks, width, n_k, groups, seed,
-                    device, compat, solvers, a * dx, 2 * a * dx)
+                    device, compat, solvers, a * dx, 2 * a * dx, electrodes)
 
 
 def run_dipole_dipole_survey_25d(sc: Scenario, n_walks: int, n_max: int = 4, width: float = 0.5,
                                  n_k: int | None = None, groups=1, seed: int = 0, device: int | None = None,
-                                 compat: str = "fixed", solvers=None) -> Survey25DResult:
+                                 compat: str = "fixed", solvers=None, electrodes: str = "gaussian") -> Survey25DResult:
     """2.5-D dipole-dipole pseudosection: quadripoles (A, B, M, N) = (c, c+1, c+1+n, c+2+n),
     n = 1..n_max, rho_a = pi n (n+1) (n+2) a dV / I with dV = V_N - V_M (positive over a
-    half-space). The quadrature covers the electrode distances a .. (n_max + 2) a."""
+    half-space). The quadrature covers the electrode distances a .. (n_max + 2) a.
+    electrodes: as in run_wenner_survey_25d."""
     quad = dipole_dipole_quadripoles(len(sc.points), n_max)
     x = np.asarray(sc.points, np.float64)
     dx = float(np.linalg.norm(x[1] - x[0])) if len(x) > 1 else 1.0
@@ -263,4 +277,4 @@ def run_dipole_dipole_survey_25d(sc: Scenario, n_walks: int, n_max: int = 4, wid
         return np.array([dipole_dipole_geometric_factor(dx, int(v)) for v in n])
 
     return _run_25d(sc, quad, [0, 1], lambda q: (q[:, 3], q[:, 2]), factor, n_walks, width, n_k, groups, seed,
-                    device, compat, solvers, dx, (n_max + 2) * dx)
+                    device, compat, solvers, dx, (n_max + 2) * dx, electrodes)

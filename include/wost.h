@@ -315,6 +315,61 @@ int wost_set_wavenumbers(wost_handle* h, const double* k2, int32_t n);
 /* Values a solve of the handle scores per walk: max(1, wavenumbers) * wost_num_sources. */
 int wost_num_channels(const wost_handle* h, int32_t* n_channels);
 
+/* Point sources (compat="fixed"; no reference counterpart). A DC survey injects
+ * current at points. With f = sum_p q_p delta(z_p) the source integral of a Walk-on-Stars
+ * step, int G_B(x, y) f(y) dy over the star-shaped region, is sum_p q_p G_B(x, z_p) over the
+ * charges inside the step's ball and visible from x, G_B being the ball's Green's function
+ * that the sampled estimator integrates: nothing is sampled, no width exists and no sample can
+ * miss. wost_set_point_sources gives the handle n charges (n = 0 clears them); charge p has
+ * position (x, y), strength (the current that enters the 2-D domain) and belongs to source
+ * channel source in [0, n_sources). wost_num_sources then reports n_sources, wost_num_channels
+ * max(1, wavenumbers) * n_sources, and wost_solve_multi / wost_solve_range /
+ * wost_solve_distributed (wost_solve when there is one channel) score the charges with the
+ * channel layout they document. Each channel's sums are bit for bit those of a solve of that
+ * source's charges alone. Positions and strengths are read at run time: one compiled kernel
+ * per (problem, n, n_sources, wavenumbers) serves every electrode set. Charges on the Neumann
+ * polyline (surface electrodes) are found by the host, with the segment(s) they lie on; a
+ * query point on the Neumann polyline starts its walks as boundary points (inward
+ * directions, the half-ball's factor 2), for which the two polylines must close the domain.
+ * A charge closer to the walker than eps / 2 scores as at eps / 2 (an electrode of that
+ * radius), so a query point that is itself a charge gives a finite value.
+ *   WOST_ERR_INVALID_ARG  n > WOST_MAX_POINT_CHARGES, n_sources < 1 (with n > 0), n_sources x
+ *                         wavenumbers > WOST_MAX_SOURCES, a source outside [0, n_sources) or
+ *                         without a charge, a non-finite position or strength, or a handle
+ *                         that has a source field (mixing the two is not supported;
+ *                         wost_set_field / wost_set_sources with a source likewise refuse
+ *                         while charges are set);
+ *   WOST_ERR_UNSUPPORTED  a compat="reference" handle (its source sample is tied to the
+ *                         step's direction, Q13, and drawn without the Jacobian, Q3: its
+ *                         expectation is not int G f, so no exact counterpart exists).
+ * Needs the field-specialised kernel (WOST_ERR_UNSUPPORTED from the solve when wost_set_jit
+ * disabled it); such a solve never races its compile. wost_solve_history refuses a handle
+ * with charges (WOST_ERR_UNSUPPORTED): a step has no single sample point to record. */
+#define WOST_MAX_POINT_CHARGES 32
+typedef struct {
+    float x, y;
+    float strength;
+    int32_t source;
+} wost_point_charge;
+int wost_set_point_sources(wost_handle* h, const wost_point_charge* charges, int32_t n, int32_t n_sources);
+/* The handle's charge count and a checksum (FNV-1a 64) of the charges and n_sources (0, 0
+ * when none is set); wost_solve_distributed's agreement key carries it. */
+int wost_point_sources_info(const wost_handle* h, int32_t* n, uint64_t* checksum);
+/* The ball's Green's function with its pole at the centre, as the kernels evaluate it (host
+ * only, no device): out[i] = ln(R[i] / r[i]) / (2 pi) for sigma_bar == 0, else
+ * [K0(t) - K0(s) I0(t) / I0(s)] / (2 pi) with t = r sqrt(sigma_bar), s = R sqrt(sigma_bar)
+ * (float32 polynomials of Abramowitz & Stegun 9.8.1-9.8.6, exponentially scaled: finite for
+ * every s). 0 < r < R. */
+int wost_ball_greens(double sigma_bar, const float* r, const float* R, int64_t n, float* out);
+/* The kernels' visibility predicate on the host (no device), with the scan kernels' nearest-
+ * crossing query: out[i] = 1 when charge (charges[2i], charges[2i+1]) is visible from point
+ * (points[2i], points[2i+1]) in the domain bounded by the Neumann polyline `neumann`.
+ * point_segments[i] (NULL: all interior): 0 for an interior point, seg + 1 for a point on
+ * segment seg whose left normal points into the domain, -(seg + 1) when its right normal
+ * does. The charge's own segment(s) are found as wost_set_point_sources finds them. */
+int wost_point_visible(const wost_polyline* neumann, const float* points, const int32_t* point_segments,
+                       const float* charges, int64_t n, uint8_t* out);
+
 int wost_last_timing(const wost_handle* h, wost_timing* out);
 
 /* Number of source fields the handle scores (1, or n of wost_set_sources). */
@@ -528,6 +583,13 @@ int wost_kernel_source_sources(const wost_problem* problem, const wost_field* co
  * multi-wavenumber kernel. */
 int wost_kernel_source_channels(const wost_problem* problem, const wost_field* const* sources, int32_t n_sources,
                                 int32_t n_wavenumbers, char* out, int64_t capacity, int64_t* length);
+
+/* The same for a handle with n_charges point charges in n_sources source channels
+ * (wost_set_point_sources; the problem must have no source field) and n_wavenumbers
+ * wavenumbers: the source depends on the counts only, never on positions or strengths. With
+ * wost_set_point_sources' refusals (compat="reference": WOST_ERR_UNSUPPORTED). */
+int wost_kernel_source_points(const wost_problem* problem, int32_t n_charges, int32_t n_sources, int32_t n_wavenumbers,
+                              char* out, int64_t capacity, int64_t* length);
 
 /* Compiles a generated walk-kernel source (wost_kernel_source) for the gfx target `arch`
  * ("gfx950") with the compile options of a new handle, without a device: in the compile

@@ -1,0 +1,280 @@
+"""Point sources on the host (include/wost.h wost_set_point_sources): the
+ball's Green's function as the kernels evaluate it (wost_ball_greens) against scipy, its
+integral against the existing G_norm (wost_greens_norm), the visibility predicate
+(wost_point_visible) on the cases that surface electrodes raise, the argument checks that
+need no device, and the generated kernel source. No device is used."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+
+from dcrmontecarlo_amd import _lib
+from dcrmontecarlo_amd import scenarios as S
+from dcrmontecarlo_amd import survey
+from dcrmontecarlo_amd.geometry import PolyLinesSimple
+from dcrmontecarlo_amd.solvers import WoStSolver as W
+
+TWO_PI = 2.0 * math.pi
+
+
+def _ball_greens(sigma_bar, r, R):
+    r = np.ascontiguousarray(r, np.float32)
+    R = np.ascontiguousarray(np.broadcast_to(np.asarray(R, np.float32), r.shape))
+    out = np.empty_like(r)
+    _lib.check(_lib.lib.wost_ball_greens(float(sigma_bar), _lib.fptr(r), _lib.fptr(R), r.size, _lib.fptr(out)),
+               "wost_ball_greens")
+    return out
+
+
+def _ulp32(x):
+    return np.spacing(np.abs(x).astype(np.float32)).astype(np.float64)
+
+
+# ---- wost_ball_greens against scipy ---------------------------------------------------------
+def test_ball_greens_against_scipy():
+    """[K0(t) - K0(s) I0(t) / I0(s)] / 2 pi and ln(R / r) / 2 pi in double (scipy, exponentially
+    scaled so that the reference itself neither overflows nor underflows early), at r / R from
+    1e-4 to 0.999 and s = R sqrt(sigma_bar) from 1e-3 to 400, log-spaced, for three sigma_bar.
+    The reference takes the function's own float32 inputs (r, R and the kernels' constant
+    float32(sqrt(sigma_bar))) as exact.
+
+    Bound: the published absolute errors of the polynomials (A&S 9.8.1-9.8.6), carried
+    through the formula, plus 8 float32 ulps of the larger of the two terms subtracted:
+      first term   eK(t)                         eK(x) = 1e-8 (x <= 2), 1.9e-7 exp(-x) / sqrt(x) (x > 2)
+      second term  eK(s) I0(t)/I0(s) + K0(s) I0(t)/I0(s) (eI(t) + eI(s))
+                                                 eI(x) = 1.6e-7 / I0(x) (x <= 3.75),
+                                                         1.9e-7 / (sqrt(x) exp(-x) I0(x)) (x > 3.75), relative
+    all over 2 pi. Measured: the largest error is 0.91 of its bound (sigma_bar = 1, s = 11.3,
+    r / R = 0.17, where the first term alone counts); the rounding alone, without the
+    polynomial terms, reaches 1.09 x 8 ulps of the larger term."""
+    from scipy.special import i0e, k0e
+
+    def eK(x):
+        return np.where(x <= 2.0, 1e-8, 1.9e-7 * np.exp(-x) / np.sqrt(x))
+
+    def eI(x):
+        return np.where(x <= 3.75, 1.6e-7 / (i0e(x) * np.exp(np.minimum(x, 700.0))), 1.9e-7 / (np.sqrt(x) * i0e(x)))
+
+    ratio = np.geomspace(1e-4, 0.999, 48)
+    worst = (0.0, None)
+    for sb in (1.0, 6.0, 1080.9):
+        sq = float(np.float32(math.sqrt(sb)))
+        for s in np.geomspace(1e-3, 400.0, 48):
+            R = np.float32(s / sq)
+            r = (ratio * float(R)).astype(np.float32)
+            r = r[r < R]
+            got = _ball_greens(sb, r, R).astype(np.float64)
+            assert np.all(np.isfinite(got))
+            t, ss = r.astype(np.float64) * sq, float(R) * sq
+            first = k0e(t) * np.exp(-t)
+            second = k0e(ss) * i0e(t) / i0e(ss) * np.exp(t - 2.0 * ss)
+            want = (first - second) / TWO_PI
+            k0s_ratio = second                      # K0(s) I0(t) / I0(s)
+            i_ratio = i0e(t) / i0e(ss) * np.exp(t - ss)
+            bound = (eK(t) + eK(np.float64(ss)) * i_ratio + k0s_ratio * (eI(t) + eI(np.float64(ss)))
+                     + 8.0 * _ulp32(np.maximum(first, second))) / TWO_PI
+            q = np.abs(got - want) / bound
+            if q.max() > worst[0]:
+                worst = (float(q.max()), (sb, float(ss), float(r[q.argmax()] / R)))
+            assert np.all(np.abs(got - want) <= bound), (sb, ss, q.max())
+    print("largest error / bound", worst)
+    # C4-like balls: at s = 400 the second term is gone and the result is K0(t) / 2 pi
+    R = np.float32(400.0)
+    r = (np.geomspace(1e-4, 0.999, 48) * 400.0).astype(np.float32)
+    got = _ball_greens(1.0, r, R).astype(np.float64)
+    t = r.astype(np.float64)
+    k0t = k0e(t) * np.exp(-t)
+    assert np.all(np.isfinite(got))
+    assert np.all(np.abs(got - k0t / TWO_PI) <= (eK(t) + 8.0 * _ulp32(k0t)) / TWO_PI)
+    # the logarithm: sigma_bar = 0
+    r = np.geomspace(1e-4, 0.999, 200).astype(np.float32)
+    got = _ball_greens(0.0, r, 1.0).astype(np.float64)
+    want = -np.log(r.astype(np.float64)) / TWO_PI
+    err = np.abs(got - want)
+    print("logarithm: largest error in ulps of the value", (err / _ulp32(want)).max())
+    # two roundings (the quotient, the logarithm's own ulp) and the product's: 3 ulps of the
+    # value, plus the quotient's half ulp seen through d ln = d(R / r) / (R / r)
+    assert np.all(err <= 3.0 * _ulp32(want) + 2.0 ** -24 / TWO_PI)
+    # small s recovers the logarithm (no cancellation of the two terms' logarithms)
+    g0 = _ball_greens(1e-8, r, 1.0).astype(np.float64)
+    assert np.all(np.abs(g0 - want) <= 4.0 * _ulp32(want) + 2.0 ** -24 / TWO_PI)
+
+
+def test_ball_greens_rejects_bad_arguments():
+    r = np.ones(2, np.float32)
+    out = np.empty(2, np.float32)
+    assert _lib.lib.wost_ball_greens(-1.0, _lib.fptr(r), _lib.fptr(r), 2, _lib.fptr(out)) == _lib.WOST_ERR_INVALID_ARG
+    assert _lib.lib.wost_ball_greens(1.0, None, None, 2, None) == _lib.WOST_ERR_INVALID_ARG
+    # on and outside the sphere the screened function is 0
+    assert _ball_greens(4.0, np.float32([1.0, 2.0]), np.float32([1.0, 1.0])).tolist() == [0.0, 0.0]
+
+
+# ---- its integral is the G_norm the estimator already uses ------------------------------------
+@pytest.mark.parametrize("x", [0.1, 1.0, 5.0, 30.0])
+def test_ball_greens_integrates_to_greens_norm(x):
+    """int_0^R G(r) 2 pi r dr = (1 - 1 / I0(R sqrt(sigma_bar))) / sigma_bar = wost_greens_norm,
+    to the rtol = 4e-7 at which tests/test_greens_table.py pins that function to its closed
+    form. Gauss-Legendre (24 nodes) in double on wost_ball_greens values over panels graded
+    geometrically towards the logarithmic pole at r = 0 and the zero at r = R."""
+    sb = 2.40625
+    sq = float(np.float32(math.sqrt(sb)))
+    R = np.float32(x / sq)
+    gn = np.empty(1, np.float32)
+    Ra = np.array([R], np.float32)
+    _lib.check(_lib.lib.wost_greens_norm(sb, _lib.fptr(Ra), 1, _lib.fptr(gn)), "wost_greens_norm")
+    nodes, weights = np.polynomial.legendre.leggauss(24)
+    edges = np.concatenate([[0.0], float(R) * np.geomspace(1e-9, 0.5, 40), float(R) * (1.0 - np.geomspace(0.5, 1e-9, 40)[1:]),
+                            [float(R)]])
+    total = 0.0
+    for a, b in zip(edges[:-1], edges[1:]):
+        r = (0.5 * (b - a) * nodes + 0.5 * (a + b)).astype(np.float32)   # the function takes float32 radii
+        ok = (r > 0) & (r < R)
+        g = np.zeros(r.shape)
+        g[ok] = _ball_greens(sb, r[ok], R)
+        total += 0.5 * (b - a) * float(np.sum(weights * g * TWO_PI * r.astype(np.float64)))
+    print("R sqrt(sigma_bar)", x, "integral", total, "G_norm", float(gn[0]), "relative", total / float(gn[0]) - 1.0)
+    np.testing.assert_allclose(total, float(gn[0]), rtol=4e-7, atol=0)
+
+
+# ---- visibility -------------------------------------------------------------------------------
+def _visible(neumann, x, z, xseg=0):
+    """wost_point_visible for one point and one charge. xseg: 0 interior, +(seg + 1) on segment
+    seg with its left normal inward, -(seg + 1) with its right normal inward."""
+    poly, keep = _lib.make_polyline(np.asarray(neumann, np.float32))
+    p = np.asarray(x, np.float32).reshape(1, 2).copy()
+    c = np.asarray(z, np.float32).reshape(1, 2).copy()
+    code = np.array([xseg], np.int32)
+    out = np.zeros(1, np.uint8)
+    _lib.check(_lib.lib.wost_point_visible(ctypes.byref(poly), _lib.fptr(p), code.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                           _lib.fptr(c), 1, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+               "wost_point_visible")
+    return bool(out[0])
+
+
+def test_visibility_flat_segment_both_on_it():
+    """The domain lies below the polyline (drawn right to left: left normals point down)."""
+    for y in (0.0, 1.0):
+        flat = [[1, y], [-1, y]]
+        assert _visible(flat, (0.5, y), (-0.25, y), xseg=1)
+        for yy in (np.nextafter(np.float32(y), np.float32(2)), np.nextafter(np.float32(y), np.float32(-2))):
+            assert _visible(flat, (0.5, yy), (-0.25, y), xseg=1)      # x one ulp above / below the line
+            assert _visible(flat, (0.5, yy), (-0.25, y), xseg=0)      # ... as an interior point
+    # the same line split in 8: x and z on different segments of it, at vertices too
+    split = np.stack([np.linspace(1, -1, 9), np.zeros(9)], axis=1)
+    assert _visible(split, (0.6, 0.0), (-0.4, 0.0), xseg=2)
+    assert _visible(split, (0.25, 0.0), (0.0, 0.0), xseg=3)           # one segment from a vertex electrode
+    assert _visible(split, (0.25, 0.0), (0.0, 0.0), xseg=4)           # (x at a vertex: either of its segments)
+    assert _visible(split, (0.3, -0.4), (0.0, 0.0))
+
+
+def test_visibility_valley_and_hill():
+    valley = [[1, 1], [0, 0], [-1, 1]]         # V: the two slopes see each other only through the air
+    assert not _visible(valley, (0.5, 0.5), (-0.5, 0.5), xseg=1)
+    assert not _visible(valley, (-0.5, 0.5), (0.5, 0.5), xseg=2)
+    hill = [[1, -1], [0, 0], [-1, -1]]         # hill: through the ground
+    assert _visible(hill, (0.5, -0.5), (-0.5, -0.5), xseg=1)
+    assert _visible(hill, (-0.5, -0.5), (0.5, -0.5), xseg=2)
+    # z at the vertex, x interior below
+    assert _visible(hill, (0.2, -1.5), (0.0, 0.0))
+    assert _visible(valley, (0.2, -1.5), (0.0, 0.0))
+    # ... and x on a slope, z at the vertex: along its own segment
+    assert _visible(valley, (0.5, 0.5), (0.0, 0.0), xseg=1)
+    assert _visible(hill, (0.5, -0.5), (0.0, 0.0), xseg=1)
+
+
+def test_visibility_bump_between():
+    # flat surface with a valley cut into it between x and z (the air of the valley blocks)
+    surf = [[2, 0], [0.6, 0], [0.5, -1], [0.4, 0], [-2, 0]]
+    assert not _visible(surf, (1.5, -0.2), (-1.0, 0.0))
+    assert _visible(surf, (1.5, -3.0), (-1.0, 0.0))                   # from deep below: under the valley
+    assert not _visible(surf, (1.5, 0.0), (-1.0, 0.0), xseg=1)        # both on the surface, valley between
+
+
+def test_visibility_reentrant_corner():
+    """The 270-degree wedge 0 < phi < 3 pi / 2: Neumann (1, 0) -> (0, 0) -> (0, -1), right
+    normals inward."""
+    wedge = [[1, 0], [0, 0], [0, -1]]
+    e = lambda rho, deg: (rho * math.cos(math.radians(deg)), rho * math.sin(math.radians(deg)))
+    z = e(0.6, 18)
+    assert not _visible(wedge, e(0.6, 252), z)
+    assert _visible(wedge, e(0.5, 108), z)
+    # walkers on the two faces: the face phi = 0 sees z, the face phi = 3 pi / 2 does not
+    assert _visible(wedge, (0.5, 0.0), z, xseg=-1)
+    assert not _visible(wedge, (0.0, -0.5), z, xseg=-2)
+    # the corner itself sees everything
+    assert _visible(wedge, (0.0, 0.0), z, xseg=-1)
+
+
+# ---- argument checks that need no device ------------------------------------------------------
+def _square():
+    return PolyLinesSimple(np.array([[-1, -1], [1, -1], [1, 1], [-1, 1], [-1, -1]], np.float32))
+
+
+def test_facade_and_abi_refusals():
+    D = _square()
+    q = [((0.1, 0.2), 1.0)]
+    # reference mode
+    with pytest.raises(NotImplementedError, match="fixed"):
+        W.kernel_source_points(D, 0.0, n_charges=1, compat="reference")
+    # 33 charges, in the library and in the facade
+    with pytest.raises(ValueError, match="33"):
+        W.kernel_source_points(D, 0.0, n_charges=33)
+    with pytest.raises(ValueError, match="33"):
+        W.pack_point_charges([[((0.01 * i, 0.0), 1.0) for i in range(33)]])
+    assert W.pack_point_charges([[((0.01 * i, 0.0), 1.0) for i in range(32)]])[1:] == (32, 1)
+    # a source without a charge
+    with pytest.raises(ValueError, match="no charge"):
+        W.pack_point_charges([q, []])
+    with pytest.raises(ValueError, match="n_sources"):
+        W.kernel_source_points(D, 0.0, n_charges=2, n_sources=3)
+    # non-finite strength / position
+    for bad in (float("nan"), float("inf"), 1e39):
+        with pytest.raises(ValueError, match="non-finite"):
+            W.pack_point_charges([[((0.0, 0.0), bad)]])
+    with pytest.raises(ValueError, match="non-finite"):
+        W.pack_point_charges([[((float("nan"), 0.0), 1.0)]])
+    # channels: sources x wavenumbers
+    with pytest.raises(ValueError, match="channels"):
+        W.kernel_source_points(D, 0.0, alpha=1.0, n_charges=9, n_sources=9, n_wavenumbers=2)
+    # wavenumbers still need delta tracking
+    with pytest.raises(NotImplementedError):
+        W.kernel_source_points(D, 0.0, n_charges=1, n_wavenumbers=2)
+    # the C entry: NULL handle, and a handle-free look at the struct layout
+    assert ctypes.sizeof(_lib.WostPointCharge) == 16
+    assert _lib.lib.wost_set_point_sources(None, None, 0, 0) == _lib.WOST_ERR_INVALID_ARG
+
+
+def test_point_electrode_strength():
+    assert survey.point_electrode((1.0, 0.0), 3.0).charges == [((1.0, 0.0), 1.5)]
+    assert survey.point_electrode((1.0, 0.0), 3.0, surface=False).charges == [((1.0, 0.0), 3.0)]
+    d = survey.point_dipole((0.0, 0.0), (2.0, 0.0), 4.0)
+    assert d.charges == [((0.0, 0.0), 2.0), ((2.0, 0.0), -2.0)]
+    arr, n, ns = W.pack_point_charges([d, survey.point_electrode((5.0, 0.0))])
+    assert (n, ns) == (3, 2) and [c.source for c in arr] == [0, 0, 1] and arr[1].strength == -2.0
+
+
+# ---- the generated kernel source --------------------------------------------------------------
+NEW_NAMES = ("ball_greens", "point_visible", "charge_float", "boundary_code", "point_code", "charges")
+
+
+def test_kernel_source_without_charges_has_none_of_it():
+    for sc in (S.dcr_dipole(), S.laplace_square()):
+        for compat in ("reference", "fixed"):
+            src = sc.kernel_source(compat=compat)
+            assert not [n for n in NEW_NAMES if n in src]
+    assert "walk_body<true, true, true, false, false, 1, false, false>" in S.dcr_dipole().kernel_source()
+
+
+def test_kernel_source_with_charges_depends_on_the_counts_only():
+    sc = S.dcr_dipole()
+    a = sc.kernel_source_points(2, 1)
+    # (positions and strengths are no argument of the generator: two electrode sets, one source)
+    assert a == sc.kernel_source_points(2, 1)
+    assert "walk_body<true, true, true, false, false, 1, true, false, 1, 2>" in a
+    assert "wost_point_alpha_jit" in a
+    b = sc.kernel_source_points(16, 8, n_wavenumbers=2)
+    assert "#define WOST_WAVENUMBERS 1" in b and "walk_body<true, true, true, false, false, 8, true, false, 2, 16>" in b
+    lap = S.laplace_square().kernel_source_points(3, 2)
+    assert "walk_body<false, true, false, false, false, 2, true, false, 1, 3>" in lap
+    assert a != b != lap

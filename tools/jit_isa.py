@@ -4,7 +4,8 @@
 Generates the kernel source libwost would hand to hiprtc (wost_kernel_source),
 compiles it with hipcc for gfx950 with hiprtc's options, and prints the
 kernel's resource usage and an instruction histogram (static counts).
-Usage: python tools/jit_isa.py dcr_dipole [--out build/jit] [--show] [--wavenumbers NK] [--sources NS]"""
+Usage: python tools/jit_isa.py dcr_dipole [--out build/jit] [--show] [--wavenumbers NK] [--sources NS]
+       [--point-charges PC]   (point sources: PC charges in NS sources, compat="fixed")"""
 import argparse
 import collections
 import os
@@ -24,6 +25,8 @@ def main():
     ap.add_argument("--waves", default=None, help="WOST_JIT_WAVES for the generator")
     ap.add_argument("--wavenumbers", type=int, default=0, help="NK: wavenumbers per walk (set_wavenumbers; 0: none)")
     ap.add_argument("--sources", type=int, default=0, help="NS: copies of the scenario's source (solve_sources; 0: its own)")
+    ap.add_argument("--point-charges", type=int, default=0,
+                    help="PC: point charges (set_point_sources) in --sources sources, instead of the source field")
     a = ap.parse_args()
     if a.waves:
         os.environ["WOST_JIT_WAVES"] = a.waves
@@ -32,10 +35,14 @@ def main():
     kw = {"n_walks": 1}
     sc = S.ALL[a.scenario](**({"n_electrodes": 4} if a.scenario in ("dcr_dipole", "wenner_topography") else {}), **kw) \
         if a.scenario in ("dcr_dipole", "wenner_topography") else S.ALL[a.scenario]()
-    src = sc.kernel_source(n_wavenumbers=a.wavenumbers, **({"sources": [sc.f * (1.0 + k) for k in range(a.sources)]}
-                                                           if a.sources else {}))
+    if a.point_charges:
+        src = sc.kernel_source_points(a.point_charges, max(a.sources, 1), n_wavenumbers=a.wavenumbers)
+    else:
+        src = sc.kernel_source(n_wavenumbers=a.wavenumbers, **({"sources": [sc.f * (1.0 + k) for k in range(a.sources)]}
+                                                               if a.sources else {}))
     os.makedirs(a.out, exist_ok=True)
-    tag = a.scenario + (f"_nk{a.wavenumbers}" if a.wavenumbers else "") + (f"_ns{a.sources}" if a.sources else "")
+    tag = a.scenario + (f"_nk{a.wavenumbers}" if a.wavenumbers else "") + (f"_ns{a.sources}" if a.sources else "") + (
+        f"_pc{a.point_charges}" if a.point_charges else "")
     hip = os.path.join(a.out, f"{tag}.hip")
     with open(hip, "w") as f:
         f.write(src)
