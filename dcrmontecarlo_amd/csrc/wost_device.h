@@ -2083,7 +2083,7 @@ WOST_HD float boundary_corner_radius(VP sv, int nv, float px, float py, int xcod
 // nearest(ox, oy, ex, ey, len): the nearest-crossing query of the kernel (the scans'
 // intersect_polylines_ray, the tree's intersect_polylines_tree<false, true>) from o
 // along e, a hit when within len. xcode: boundary_code of x. zs0, zs1: the segment(s)
-// z lies on (two at a vertex), or -1. sv: the polyline's vertices (x's segment only).
+// z lies on (two at a vertex), or -1. sv: the polyline's vertices (x's and z's segments only).
 // Survey electrodes lie ON the Neumann surface and so does the walker after a Neumann
 // hit, so the ray starts or ends on a segment or runs along one; crossings with x's
 // own and z's own segments say nothing and are passed over:
@@ -2092,9 +2092,9 @@ WOST_HD float boundary_corner_radius(VP sv, int nv, float px, float py, int xcod
 //     coordinates' rounding) -- without this the two slopes of a V-shaped valley would
 //     see each other through the air, since both their segments are passed over;
 //  3. from x towards z: a miss is visible, a crossing of another segment is blocked, and
-//     a crossing of x's or z's own segment moves the origin there and asks again (a line
-//     crosses each of the at most three such segments once; four queries at the most,
-//     then blocked).
+//     a crossing of x's or z's own segment moves the origin beyond it and asks again (a
+//     line crosses each of the at most three such segments once; four queries at the
+//     most, then blocked).
 // A ray that leaves x inwards (2.) and meets no other segment stays inside until z, so z's
 // side needs no test of its own.
 template <class VP, class Query>
@@ -2119,8 +2119,23 @@ WOST_HD bool point_visible(VP sv, float px, float py, int xcode, float zx, float
         const Hit h = nearest(ox, oy, ex, ey, len);
         if (!h.hit) return true;
         if (h.seg != xs && h.seg != zs0 && h.seg != zs1) return false;
-        ox = h.x;
-        oy = h.y;
+        // An own segment: the line meets it once, within the coordinates' rounding of x or
+        // of z. A new origin AT the crossing is again within that rounding of the segment, on
+        // either side of it, and the next query can report the same crossing (a walker whose
+        // float32 position fell on the outer side of its segment used up all four queries
+        // that way and read "blocked"). So the origin goes beyond the crossing by the length
+        // over which the ray leaves the rounding's band around the segment, noise / sin(angle);
+        // a z no farther than that is the crossing itself.
+        const float2 a = sv[h.seg], b = sv[h.seg + 1];
+        const float ux = b.x - a.x, uy = b.y - a.y;
+        const float noise = scale + 9.5367431640625e-07f * ((fabsf(a.x) + fabsf(a.y)) + (fabsf(b.x) + fabsf(b.y)));
+        const float cr = fabsf(ux * ey - uy * ex);                  // |u| |e| sin(angle)
+        const float step = (noise * (fabsf(ux) + fabsf(uy))) * len / cr;
+        const float rx = zx - h.x, ry = zy - h.y;
+        if (!(step < sqrtf(rx * rx + ry * ry))) return true;        // (also a ray along the segment, cr = 0)
+        const float k = step / len;
+        ox = h.x + k * ex;
+        oy = h.y + k * ey;
     }
     return false;
 }

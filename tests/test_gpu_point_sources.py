@@ -9,7 +9,18 @@ The statistical rule. Polygonal Dirichlet arcs are regular with circumradius 1, 
 monotonicity of the Green's function brackets the polygon's solution between the closed
 forms of the inscribed disk (radius cos(pi / n) for an n-gon) and of the unit disk:
     G_in - 4 se <= mean <= G_out + 4 se    and    se <= 0.02 G_out,
-se being the solve's own standard error. The 2% cap is a sizing condition."""
+se being the solve's own standard error. The 2% cap is a sizing condition.
+
+What this file pins, and what it does not. These cases are statistical: they check the
+multi-step walk -- the estimator's expectation, the weights carried from step to step, the
+boundary codes after Neumann hits -- to a few standard errors, i.e. to about 1%. The score of a
+single step is pinned deterministically elsewhere, in tests/test_gpu_point_sources_step.py:
+one-step solves against the double closed form, to a bound of a few float32 ulps derived from
+the device's operations -- ball_greens and the three ranges of ball_greens_screened on the
+device's own arithmetic, the in-ball edge, the rmin clamp, the t = 88 cut-off, alpha(z_p),
+the factor 2 and the corner radius of a surface point, point_code, visibility through the scan
+and the tree kernel, and the source and wavenumber channel mapping. The bit-equalities below
+(channel against single solve, tree against scan, shards) say nothing about the value itself."""
 import dataclasses
 import functools
 import math
