@@ -16,6 +16,7 @@
 #include <thread>
 #include <set>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -219,9 +220,10 @@ struct wost_handle {
     // field-specialised walk kernel (wost_jit.cpp)
     bool jit_enabled = true;
     hipFunction_t jit_fn = nullptr;
-    hipFunction_t jit_alpha_fn = nullptr;   // the same module's wost_point_alpha_jit (delta modes)
-    int jit_mode = -1;
-    uint64_t jit_version = ~0ull;
+    hipFunction_t jit_alpha_fn = nullptr;   // the same module's wost_point_alpha_jit (delta tracking)
+    std::optional<KernelVariant> jit_variant;   // the variant jit_fn was looked up for (empty: none)
+    uint64_t jit_version = ~0ull;               // ... and the program's version then
+    bool jit_cached(const KernelVariant& v) const { return jit_variant == v && jit_version == prog_version; }
     std::string jit_error;
 
     // Neumann segment tree (wost_tree.h): used when the Neumann polyline has at
@@ -293,9 +295,6 @@ int upload_program(wost_handle* h) {
     return WOST_OK;
 }
 
-// The field-specialised kernel for `mode` (with the walk recorder compiled in
-// when `record`), or nullptr when it is disabled or could not be built (the
-// precompiled kernel is used then; same results).
 // wost_set_trig's choice for this handle: WOST_TRIG_AUTO is exact for a Neumann polyline
 // of >= 3 segments (a curved boundary, where a direction's last ulp decides where the
 // walk goes), the hardware's sin/cos otherwise
@@ -304,50 +303,34 @@ bool exact_trig_of(const wost_handle* h) {
     return (int)(h->nverts.size() / 2) - 1 >= 3;
 }
 
-// The source of the field-specialised kernel for `mode` with the program `prog` (the
-// handle's own, or wost_prepare_multi's with other sources): the handle's polylines,
-// options and trig choice, the launch's workgroup, staging and polyline placement.
-int jit_source(const wost_handle* h, const Program& prog, int mode, bool record, int ns, int block,
-               bool global_polylines, int tree_stage, std::string* src) {
-    const int nk = mode_delta(mode) ? h->n_wavenumbers : 0;   // (0: none set, the kernel without the k2 read)
+// The source of the field-specialised kernel `v` with the program `prog` (the handle's own,
+// or wost_prepare_sources' with other sources) and the handle's polylines and options.
+// seg_phi: the segment angles a compiled-in Neumann polyline carries; null: the device's.
+int jit_source(const wost_handle* h, const Program& prog, const KernelVariant& v, const float* seg_phi,
+               std::string* src) {
     const int nn = (int)(h->nverts.size() / 2);
-    std::vector<float> phi;   // a compiled-in Neumann polyline carries the device's segment angles
-    if (jit_const_neumann(h->opt, mode, nn) && nn >= 2) {
+    std::vector<float> phi;
+    if (!seg_phi && jit_const_neumann(h->opt, v.traits, nn) && nn >= 2) {
         phi.resize(nn - 1);
         HIP_TRY(hipMemcpy(phi.data(), h->d_seg_phi, sizeof(float) * phi.size(), hipMemcpyDeviceToHost));
+        seg_phi = phi.data();
     }
-    *src = jit_generate(h->opt, mode, *prog.hdr(), prog.terms(), prog.factors(), h->dverts.data(),
-                        (int)(h->dverts.size() / 2), h->nverts.data(), nn, record, ns, block,
-                        phi.empty() ? nullptr : phi.data(), global_polylines, tree_stage, exact_trig_of(h), nk,
-                        (int)h->charges.size());
+    *src = jit_generate(h->opt, v, ProgramView{prog.hdr(), prog.terms(), prog.factors()},
+                        PolylineView{h->dverts.data(), (int)(h->dverts.size() / 2), h->nverts.data(), nn, seg_phi});
     return WOST_OK;
-}
-
-// The handle's key of a kernel variant: everything its source depends on besides the
-// program (prog_version): the staging level, the exact workgroup size (a multiple of 64,
-// at most 1024) and the trig choice
-int jit_key(const wost_handle* h, int mode, bool record, int ns, int block, bool global_polylines, int tree_stage) {
-    const bool exact = exact_trig_of(h);
-    const int nk = mode_delta(mode) ? h->n_wavenumbers : 0;
-    const int pc = (int)h->charges.size();   // (the count only: the charges are run-time data)
-    return (((((((2 * mode + (record ? 1 : 0)) * (WOST_MAX_SOURCES + 1) + ns) * (WOST_MAX_SOURCES + 1) + nk) * 3 +
-               tree_stage) * 17 + block / 64) * 2 + (global_polylines ? 1 : 0)) * 2 + (exact ? 1 : 0)) *
-               (WOST_MAX_POINT_CHARGES + 1) + pc;
 }
 
 // jit_kernel without blocking on a compile (option jit_race): kReady with the handle's
 // kernel set, kStarted when its compile began now in the background (ticket), else kWait.
-JitTry jit_kernel_try(wost_handle* h, int mode, int block, bool global_polylines, int tree_stage, JitTicket* ticket) {
+JitTry jit_kernel_try(wost_handle* h, const KernelVariant& v, JitTicket* ticket) {
     if (!h->jit_enabled) return JitTry::kWait;
-    const int key = jit_key(h, mode, false, 1, block, global_polylines, tree_stage);
-    if (h->jit_mode == key && h->jit_version == h->prog_version && h->jit_fn) return JitTry::kReady;
+    if (h->jit_cached(v) && h->jit_fn) return JitTry::kReady;
     std::string src, err;
-    if (jit_source(h, h->prog, mode, false, 1, block, global_polylines, tree_stage, &src) != WOST_OK)
-        return JitTry::kWait;
+    if (jit_source(h, h->prog, v, nullptr, &src) != WOST_OK) return JitTry::kWait;
     hipFunction_t fn = nullptr, afn = nullptr;
     const JitTry r = jit_try_kernel(h->opt, h->device, src, &fn, &afn, ticket, &err);
-    if (r == JitTry::kReady && (!mode_delta(mode) || afn)) {
-        h->jit_mode = key;
+    if (r == JitTry::kReady && (!v.traits.delta || afn)) {
+        h->jit_variant = v;
         h->jit_version = h->prog_version;
         h->jit_fn = fn;
         h->jit_alpha_fn = afn;
@@ -355,30 +338,31 @@ JitTry jit_kernel_try(wost_handle* h, int mode, int block, bool global_polylines
     return r;
 }
 
-hipFunction_t jit_kernel(wost_handle* h, int mode, bool record, int ns = 1, int block = kWalkBlock,
-                         bool global_polylines = false, int tree_stage = 0, double* compile_ms = nullptr) {
+// The field-specialised kernel `v` of the handle's program, or nullptr when it is disabled
+// or could not be built (the precompiled kernel is used then; same results). *compile_ms
+// grows by the host time of a compile.
+hipFunction_t jit_kernel(wost_handle* h, const KernelVariant& v, double* compile_ms) {
     if (!h->jit_enabled) return nullptr;
-    const int key = jit_key(h, mode, record, ns, block, global_polylines, tree_stage);
-    if (h->jit_mode == key && h->jit_version == h->prog_version) return h->jit_fn;
+    if (h->jit_cached(v)) return h->jit_fn;
     h->jit_fn = nullptr;
     h->jit_alpha_fn = nullptr;
-    h->jit_mode = key;
+    h->jit_variant = v;
     h->jit_version = h->prog_version;
     std::string src;
-    if (jit_source(h, h->prog, mode, record, ns, block, global_polylines, tree_stage, &src) != WOST_OK) return nullptr;
+    if (jit_source(h, h->prog, v, nullptr, &src) != WOST_OK) return nullptr;
     std::string err;
     hipFunction_t fn = nullptr;
     hipFunction_t afn = nullptr;
     double cms = 0.0;
     const bool ok = jit_get_kernel(h->opt, h->device, src, &fn, &err, &afn, &cms);
-    if (compile_ms) *compile_ms += cms;
+    *compile_ms += cms;
     if (!ok) {
         h->jit_error = err;
         std::fprintf(stderr, "libwost: field-specialised kernel unavailable, using the precompiled one: %s\n",
                      err.c_str());
         return nullptr;
     }
-    if (mode_delta(mode) && !afn) {
+    if (v.traits.delta && !afn) {
         h->jit_error = "the specialised module has no wost_point_alpha_jit";
         return nullptr;
     }
@@ -568,10 +552,10 @@ float silhouette_stop2(float rmin) {
 // stage and sets the workgroup size and the vertices to stage.
 constexpr size_t kTreeLdsMaxBytes = 64 * 1024;
 constexpr int kTreeLdsDefaultLevel = 2;
-int tree_lds_records(const wost_handle* h, int mode, int level, int* block, int* verts) {
+int tree_lds_records(const wost_handle* h, const WalkTraits& t, int level, int* block, int* verts) {
     *block = kWalkBlock;
     *verts = 0;
-    if (!mode_tree(mode) || !h->tree_ready) return 0;
+    if (!t.tree || !h->tree_ready) return 0;
     level = std::min(level, h->opt.tree_lds);
     const int n = h->tree.first_leaf;
     if (level <= 0 || n <= 0 || (size_t)n * 8 * sizeof(float4) > kTreeLdsMaxBytes) return 0;
@@ -589,21 +573,15 @@ bool use_tree(const wost_handle* h) {
     return nseg >= 1 && h->tree_min_segments >= 0 && nseg >= h->tree_min_segments;
 }
 
-int walk_mode_src(const wost_handle* h, bool src) {
+// The traits of the handle's walks with a source term or not (delta tracking needs one:
+// check_request refuses the solve without).
+WalkTraits walk_traits(const wost_handle* h, bool src) {
     const bool neu = !h->nverts.empty();
-    const bool tree = neu && use_tree(h);
-    if (h->compat == WOST_COMPAT_FIXED) {   // the nearest-crossing ray queries (scan or tree)
-        if (h->delta) return neu ? (tree ? MODE_FIX_MIXED_DELTA_TREE : MODE_FIX_MIXED_DELTA) : MODE_FIX_DELTA;
-        if (neu) return src ? (tree ? MODE_FIX_MIXED_POISSON_TREE : MODE_FIX_MIXED_POISSON)
-                            : (tree ? MODE_FIX_MIXED_TREE : MODE_FIX_MIXED);
-        return src ? MODE_FIX_POISSON : MODE_FIX_DIRICHLET;
-    }
-    if (h->delta) return neu ? (tree ? MODE_MIXED_DELTA_TREE : MODE_MIXED_DELTA) : MODE_DELTA;
-    if (neu) return src ? (tree ? MODE_MIXED_POISSON_TREE : MODE_MIXED_POISSON) : (tree ? MODE_MIXED_TREE : MODE_MIXED);
-    return src ? MODE_POISSON : MODE_DIRICHLET;
+    return WalkTraits{.neu = neu, .src = src || h->delta, .delta = h->delta, .tree = neu && use_tree(h),
+                      .fix = h->compat == WOST_COMPAT_FIXED};
 }
 
-int walk_mode(const wost_handle* h) { return walk_mode_src(h, h->has_source()); }
+WalkTraits walk_traits(const wost_handle* h) { return walk_traits(h, h->has_source()); }
 
 int ensure_tree(wost_handle* h) {
     if (h->tree_ready) return WOST_OK;
@@ -987,7 +965,7 @@ SolveRequest whole_request(const float* points, int64_t n_points, int64_t W, int
     return rq;
 }
 
-// The kernel a solve of n_points launches first (its occupancy fallback may then stage
+// The kernel a solve launches first (its occupancy fallback may then stage
 // less): the workgroup, the segment tree's staging, and whether the polylines are read
 // from global memory. Shared by choose_kernel, solve_race and wost_prepare_sources, so that
 // a raced or prepared kernel is the one the solve looks up.
@@ -998,28 +976,38 @@ struct KernelShape {
     int stage() const { return tree_lds > 0 ? (tree_verts > 0 ? 2 : 1) : 0; }
 };
 
-int first_kernel_shape(const wost_handle* h, int mode, int64_t n_points, KernelShape* ks) {
+// The field-specialised kernel of that shape for walks with traits `t` that score n_sources
+// sources: the one place that reads the rest of the variant off the handle.
+KernelVariant kernel_variant(const wost_handle* h, const WalkTraits& t, const KernelShape& ks, bool record,
+                             int n_sources) {
+    return KernelVariant{.traits = t, .record = record, .n_sources = n_sources,
+                         .n_wavenumbers = t.delta ? h->n_wavenumbers : 0,   // (0: the kernel without the k2 read)
+                         .n_charges = (int)h->charges.size(), .block = ks.block, .global_polylines = ks.gpoly,
+                         .tree_stage = ks.stage(), .exact_trig = exact_trig_of(h)};
+}
+
+int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* ks) {
     *ks = KernelShape{};
-    ks->tree_lds = h->jit_enabled ? tree_lds_records(h, mode, ks->tree_level, &ks->block, &ks->tree_verts) : 0;
+    ks->tree_lds = h->jit_enabled ? tree_lds_records(h, t, ks->tree_level, &ks->block, &ks->tree_verts) : 0;
     // option walk_block: the workgroup of the field-specialised scan kernels (a multiple of
     // 64 up to 1024): larger workgroups share one LDS copy of the sampler and G_norm tables,
     // so more waves fit a CU than 256-thread workgroups allow (results are the same bits)
-    if (h->jit_enabled && !mode_tree(mode) && h->opt.walk_block > 0) ks->block = h->opt.walk_block;
+    if (h->jit_enabled && !t.tree && h->opt.walk_block > 0) ks->block = h->opt.walk_block;
     const int nd_ = (int)(h->dverts.size() / 2), nn_ = (int)(h->nverts.size() / 2);
     const Options& O = h->opt;
     // polylines whose LDS copy would cost the walk kernel its occupancy are read from
     // global memory instead (field-specialised kernels; the precompiled ones stage them)
     // (the staged tree records have their own budget, kTreeLdsMaxBytes)
-    ks->gpoly = h->jit_enabled && walk_lds_bytes(mode, nd_, nn_, (int)n_points, 0,
-                                                 jit_const_dirichlet(O, nd_)) > kGlobalPolylineLdsBytes;
+    WalkLds lds{.traits = t, .nd = nd_, .nn = nn_, .const_d = jit_const_dirichlet(O, nd_)};
+    ks->gpoly = h->jit_enabled && walk_lds_bytes(lds) > kGlobalPolylineLdsBytes;
     // the brute-force scan of a long Neumann polyline (neumann_scan_both) reads every vertex
     // at every step: staged in LDS with one 1024-thread workgroup per CU when it fits (a
     // broadcast LDS read per vertex), else from global memory
-    if (ks->gpoly && h->jit_enabled && jit_fused_neumann_scan(O, mode, nn_)) {
+    if (ks->gpoly && h->jit_enabled && jit_fused_neumann_scan(O, t, nn_)) {
         int cap = 0;
         HIP_TRY(hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device));
-        if (walk_lds_bytes(mode, nd_, nn_, (int)n_points, 0, jit_const_dirichlet(O, nd_), false, false,
-                           kTreeStageVertsBlock) <= (size_t)cap) {
+        lds.block = kTreeStageVertsBlock;
+        if (walk_lds_bytes(lds) <= (size_t)cap) {
             ks->gpoly = false;
             ks->block = kTreeStageVertsBlock;
         }
@@ -1030,36 +1018,35 @@ int first_kernel_shape(const wost_handle* h, int mode, int64_t n_points, KernelS
 // The kernel a solve launches and how it fits a CU.
 struct KernelChoice {
     hipFunction_t jfn = nullptr;   // the field-specialised kernel; null: the precompiled one
-    int block = kWalkBlock, tree_lds = 0, tree_verts = 0;
-    bool gpoly = false;
+    KernelShape shape;             // (of the precompiled one: 256 threads, nothing of the tree staged)
     size_t lds = 0;                // dynamic LDS of a workgroup
     int blocks_per_cu = 0;
     double jit_ms = 0.0;           // host time spent compiling
 };
 
 // LDS bytes per workgroup of the chosen kernel
-size_t lds_of(const wost_handle* h, int mode, int64_t n_points, const KernelChoice& kc) {
-    const int nd_ = (int)(h->dverts.size() / 2), nn_ = (int)(h->nverts.size() / 2);
+size_t lds_of(const wost_handle* h, const WalkTraits& t, const KernelChoice& kc) {
+    const int nd_ = (int)(h->dverts.size() / 2);
     const bool jit = kc.jfn != nullptr;
     // option lds_pad_bytes (occupancy studies): extra bytes of LDS per workgroup
-    return walk_lds_bytes(mode, nd_, nn_, (int)n_points, kc.tree_lds, jit && jit_const_dirichlet(h->opt, nd_),
-                          jit && jit_const_neumann(h->opt, mode, nn_), jit && kc.gpoly, kc.block, kc.tree_verts) +
+    return walk_lds_bytes({.traits = t, .nd = nd_, .nn = (int)(h->nverts.size() / 2), .tree_lds = kc.shape.tree_lds,
+                           .tree_verts = kc.shape.tree_verts, .const_d = jit && jit_const_dirichlet(h->opt, nd_),
+                           .global_polylines = jit && kc.shape.gpoly, .block = kc.shape.block}) +
            (size_t)h->opt.lds_pad_bytes;
 }
 
-// The kernel of a solve of n_points with the handle's fields: the field-specialised one of
+// The kernel of a solve with the handle's fields: the field-specialised one of
 // first_kernel_shape, staging less of the segment tree while what it stages costs the CU
 // its waves; the precompiled one when that is disabled or could not be built.
-int choose_kernel(wost_handle* h, int mode, int64_t n_points, bool record, int n_src, int ns, KernelChoice* kc) {
+int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, int ns, KernelChoice* kc) {
     *kc = KernelChoice{};
-    KernelShape ks;
+    KernelShape& ks = kc->shape;
     int rc;
-    if ((rc = first_kernel_shape(h, mode, n_points, &ks)) != WOST_OK) return rc;
-    kc->gpoly = ks.gpoly;
+    if ((rc = first_kernel_shape(h, t, &ks)) != WOST_OK) return rc;
     int lds_cap = -1;
     // looks ks up and measures its occupancy
     auto lookup = [&]() -> int {
-        kc->jfn = jit_kernel(h, mode, record, n_src, ks.block, ks.gpoly, ks.stage(), &kc->jit_ms);
+        kc->jfn = jit_kernel(h, kernel_variant(h, t, ks, record, n_src), &kc->jit_ms);
         if (!kc->jfn) {   // the precompiled kernels run 256-thread workgroups, no staged tree, one channel
             if (!h->charges.empty())
                 return fail(WOST_ERR_UNSUPPORTED, "point sources need the field-specialised kernel%s%s",
@@ -1071,17 +1058,14 @@ int choose_kernel(wost_handle* h, int mode, int64_t n_points, bool record, int n
             ks.block = kWalkBlock;
             ks.tree_lds = ks.tree_verts = 0;
         }
-        kc->block = ks.block;
-        kc->tree_lds = ks.tree_lds;
-        kc->tree_verts = ks.tree_verts;
-        kc->lds = lds_of(h, mode, n_points, *kc);
+        kc->lds = lds_of(h, t, *kc);
         kc->blocks_per_cu = 0;
         if (lds_cap < 0)
             HIP_TRY(hipDeviceGetAttribute(&lds_cap, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device));
         // a workgroup whose LDS exceeds the CU's never fits: checked here, not left to the
         // occupancy query
         if (kc->jfn && kc->lds <= (size_t)lds_cap)
-            HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&kc->blocks_per_cu, kc->jfn, kc->block, kc->lds));
+            HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&kc->blocks_per_cu, kc->jfn, ks.block, kc->lds));
         return WOST_OK;
     };
     if ((rc = lookup()) != WOST_OK) return rc;
@@ -1090,12 +1074,11 @@ int choose_kernel(wost_handle* h, int mode, int64_t n_points, bool record, int n
         // stage less (the vertices, then the records), down to reading both through L1/L2
         // from 256-thread workgroups
         ks.tree_level = ks.tree_verts > 0 ? 1 : 0;
-        ks.tree_lds = tree_lds_records(h, mode, ks.tree_level, &ks.block, &ks.tree_verts);
+        ks.tree_lds = tree_lds_records(h, t, ks.tree_level, &ks.block, &ks.tree_verts);
         if ((rc = lookup()) != WOST_OK) return rc;
     }
     if (!kc->jfn)
-        HIP_TRY(walk_occupancy(mode, (int)(h->dverts.size() / 2), (int)(h->nverts.size() / 2), (int)n_points,
-                               &kc->blocks_per_cu));
+        HIP_TRY(walk_occupancy(t, (int)(h->dverts.size() / 2), (int)(h->nverts.size() / 2), &kc->blocks_per_cu));
     if (kc->blocks_per_cu < 1)
         return fail(WOST_ERR_UNSUPPORTED, "walk kernel does not fit on a CU (polylines too large for LDS: %zu bytes)",
                     kc->lds);
@@ -1191,7 +1174,8 @@ int stage_buffers(wost_handle* h, int64_t n_points, int64_t nblk, int row, Stagi
 
 // The walk kernel's arguments that hold for every launch of the solve (the batch's and the
 // launch shape's are set per launch; the pools and point_alpha by the two steps below).
-WalkArgs fill_walk_args(const wost_handle* h, const SolveRequest& rq, int mode, const KernelChoice& kc, float* d_rec) {
+WalkArgs fill_walk_args(const wost_handle* h, const SolveRequest& rq, const WalkTraits& t, const KernelChoice& kc,
+                        float* d_rec) {
     WalkArgs a{};
     a.points = h->d_points;
     a.dverts = h->d_dverts;
@@ -1215,15 +1199,15 @@ WalkArgs fill_walk_args(const wost_handle* h, const SolveRequest& rq, int mode, 
     a.exact_trig = exact_trig_of(h) ? 1 : 0;
     for (int j = 0; j < h->n_wavenumbers; ++j) a.k2[j] = h->k2[j];   // (the rest 0)
     a.charges = h->charges.empty() ? nullptr : h->d_charges;
-    if (mode_tree(mode)) {
+    if (t.tree) {
         a.tree = reinterpret_cast<const float4*>(h->d_tree);
         a.tree_first_leaf = h->tree.first_leaf;
         a.tree_leaf = h->tree.leaf;
         a.tree_tol = h->tree.tol;
         a.tree_stop2 = silhouette_stop2(a.rmin);
         a.tree_kmax = h->tree.kmax;
-        a.tree_lds_records = kc.tree_lds;
-        a.tree_lds_verts = kc.tree_verts;
+        a.tree_lds_records = kc.shape.tree_lds;
+        a.tree_lds_verts = kc.shape.tree_verts;
         a.tree_depth = h->tree.depth;
     }
     return a;
@@ -1233,9 +1217,9 @@ WalkArgs fill_walk_args(const wost_handle* h, const SolveRequest& rq, int mode, 
 // Neumann polyline's largest extent from its bounding box; tree_pool = 0 turns them off,
 // pool_slots (default 128) walks per class and workgroup
 // (a parked walk holds one attenuation: launches of several wavenumbers run without pools)
-int setup_pools(wost_handle* h, int mode, int n_src, int blocks_per_cu, WalkArgs* a) {
+int setup_pools(wost_handle* h, const WalkTraits& t, int n_src, int blocks_per_cu, WalkArgs* a) {
     const Options& O = h->opt;
-    if (!mode_tree(mode) || O.tree_pool == 0 || h->nverts.size() < 4 || h->n_wavenumbers > 1 || !h->charges.empty())
+    if (!t.tree || O.tree_pool == 0 || h->nverts.size() < 4 || h->n_wavenumbers > 1 || !h->charges.empty())
         return WOST_OK;
     float x0 = h->nverts[0], x1 = x0, y0 = h->nverts[1], y1 = y0;
     for (size_t i = 2; i + 1 < h->nverts.size(); i += 2) {
@@ -1257,8 +1241,8 @@ int setup_pools(wost_handle* h, int mode, int n_src, int blocks_per_cu, WalkArgs
 }
 
 // Delta tracking: alpha at the query points, with the walk kernel's fields.
-int launch_point_alpha_for(wost_handle* h, int mode, hipFunction_t jfn, int64_t n_points, WalkArgs* a) {
-    if (!mode_delta(mode) || n_points <= 0) return WOST_OK;
+int launch_point_alpha_for(wost_handle* h, const WalkTraits& t, hipFunction_t jfn, int64_t n_points, WalkArgs* a) {
+    if (!t.delta || n_points <= 0) return WOST_OK;
     if (int rc = ensure_cap(h->d_point_alpha, h->point_alpha_cap, n_points)) return rc;
     if (jfn) {
         const float2* pts = h->d_points;
@@ -1345,9 +1329,9 @@ int upload_charges(wost_handle* h) {
 // A point-source solve's per-solve data: alpha at the charges with the walk kernel's own
 // fields (delta tracking; the kernel that evaluates it at the query points), and the query
 // points' boundary codes (a Neumann polyline).
-int setup_point_sources(wost_handle* h, int mode, const SolveRequest& rq, WalkArgs* a) {
+int setup_point_sources(wost_handle* h, const WalkTraits& t, const SolveRequest& rq, WalkArgs* a) {
     if (h->charges.empty()) return WOST_OK;
-    if (mode_delta(mode)) {
+    if (t.delta) {
         if (!h->jit_alpha_fn) return fail(WOST_ERR_UNSUPPORTED, "point sources need the field-specialised kernel");
         const float2* pts = reinterpret_cast<const float2*>(h->d_charges + CHG_XY);
         long long n = (long long)h->charges.size();
@@ -1356,7 +1340,7 @@ int setup_point_sources(wost_handle* h, int mode, const SolveRequest& rq, WalkAr
         void* args[] = {&prog, &pts, &n, &out};
         HIP_TRY(hipModuleLaunchKernel(h->jit_alpha_fn, 1, 1, 1, 256, 1, 1, 0, h->stream, args, nullptr));
     }
-    if (!mode_neu(mode) || rq.n_points <= 0) return WOST_OK;
+    if (!t.neu || rq.n_points <= 0) return WOST_OK;
     const int nn = (int)(h->nverts.size() / 2);
     std::vector<int32_t> code((size_t)rq.n_points, 0);
     std::vector<int32_t> seg_code((size_t)std::max(nn - 1, 0), INT32_MIN);   // (each segment's, found once)
@@ -1505,12 +1489,12 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
     const int ns = h->channels();
     const int row = 2 * ns + 1;   // doubles per block / point row
     const int64_t n_points = rq.n_points;
-    const int mode = walk_mode(h);
+    const WalkTraits t = walk_traits(h);
 
     HIP_TRY(hipSetDevice(h->device));
     if ((rc = upload_program(h)) != WOST_OK) return rc;
     if (h->has_source() && (rc = ensure_table(h)) != WOST_OK) return rc;
-    if (mode_tree(mode) && (rc = ensure_tree(h)) != WOST_OK) return rc;
+    if (t.tree && (rc = ensure_tree(h)) != WOST_OK) return rc;
     if (out.records && !h->charges.empty())
         return fail(WOST_ERR_UNSUPPORTED, "wost_solve_history does not record point sources (a step scores every "
                                           "charge in its ball: there is no sample point)");
@@ -1540,7 +1524,7 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
     // the points go with the first batch's block ranges, unless the query points' alpha
     // (delta tracking) needs them first
     bool points_pending = true;
-    if (mode_delta(mode) && n_points > 0) {
+    if (t.delta && n_points > 0) {
         HIP_TRY(hipMemcpyAsync(h->d_points, st.points, sizeof(float2) * n_points, hipMemcpyHostToDevice, h->stream));
         points_pending = false;
     }
@@ -1558,16 +1542,17 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
         HIP_TRY(hipMalloc(&d_rec, (size_t)std::min<int64_t>(R.walks_total, batch_limit) * rec_walk_bytes));
 
     KernelChoice kc;
-    if ((rc = choose_kernel(h, mode, n_points, out.records != nullptr, n_src, ns, &kc)) != WOST_OK) return rc;
-    WalkArgs a = fill_walk_args(h, rq, mode, kc, d_rec);
-    if ((rc = setup_pools(h, mode, n_src, kc.blocks_per_cu, &a)) != WOST_OK) return rc;
-    if ((rc = launch_point_alpha_for(h, mode, kc.jfn, n_points, &a)) != WOST_OK) return rc;
-    if ((rc = setup_point_sources(h, mode, rq, &a)) != WOST_OK) return rc;
+    if ((rc = choose_kernel(h, t, out.records != nullptr, n_src, ns, &kc)) != WOST_OK) return rc;
+    const int block = kc.shape.block;
+    WalkArgs a = fill_walk_args(h, rq, t, kc, d_rec);
+    if ((rc = setup_pools(h, t, n_src, kc.blocks_per_cu, &a)) != WOST_OK) return rc;
+    if ((rc = launch_point_alpha_for(h, t, kc.jfn, n_points, &a)) != WOST_OK) return rc;
+    if ((rc = setup_point_sources(h, t, rq, &a)) != WOST_OK) return rc;
 
     LaunchIn shape_in;
-    shape_in.short_walks = !mode_neu(mode);
-    shape_in.tree = mode_tree(mode);
-    shape_in.block = kc.block;
+    shape_in.short_walks = !t.neu;
+    shape_in.tree = t.tree;
+    shape_in.block = block;
     shape_in.blocks_per_cu = kc.blocks_per_cu;
     shape_in.num_cus = h->num_cus;
     shape_in.opt = &h->opt;
@@ -1607,20 +1592,20 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
         // shape the launch
         shape_in.count = count;
         const LaunchShape s = launch_shape(shape_in);
-        set_shape_args(h, s, kc.block, &a);
+        set_shape_args(h, s, block, &a);
         if ((rc = ensure_control_block(h, s.waves, &a)) != WOST_OK) return rc;   // (more waves than it holds)
 
         // walk, then reduce the blocks
         HIP_TRY(hipEventRecord(h->ev[0], h->stream));
         if (kc.jfn) {
             void* args[] = {&a};
-            HIP_TRY(hipModuleLaunchKernel(kc.jfn, s.grid, 1, 1, kc.block, 1, 1, (unsigned)kc.lds, h->stream, args, nullptr));
+            HIP_TRY(hipModuleLaunchKernel(kc.jfn, s.grid, 1, 1, block, 1, 1, (unsigned)kc.lds, h->stream, args, nullptr));
         } else {
-            HIP_TRY(launch_walk(mode, a, s.grid, h->stream));
+            HIP_TRY(launch_walk(t, a, s.grid, h->stream));
         }
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
         HIP_TRY(launch_block_reduce(h->d_val, h->d_steps, h->d_begin, nb, ns, d_rows + row * (j - R.block_begin),
-                                    h->d_counter, h->stream, mode_tree(mode) ? 0 : s.waves, d_lstats,
+                                    h->d_counter, h->stream, t.tree ? 0 : s.waves, d_lstats,
                                     launches == 0 ? 1 : 0));   // (the tree kernels keep no wave records)
         h->counter_zero = true;
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -1675,7 +1660,7 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
     h->timing.total_walks = (uint64_t)R.walks_total;
     h->timing.jit_ms = kc.jit_ms;
     h->timing.jit = kc.jfn ? 1 : 0;
-    h->timing.tree = mode_tree(mode) ? 1 : 0;
+    h->timing.tree = t.tree ? 1 : 0;
     return WOST_OK;
 }
 
@@ -1784,16 +1769,16 @@ int solve_race(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) 
     if (!points) return solve_impl(h, rq, out);
     for (int64_t i = 0; i < 2 * n_points; ++i)
         if (!std::isfinite(points[i])) return solve_impl(h, rq, out);   // (its error message)
-    const int mode = walk_mode(h);
-    if (mode_delta(mode) && !h->fields[SLOT_F].present) return solve_impl(h, rq, out);
+    const WalkTraits t = walk_traits(h);
+    if (t.delta && !h->fields[SLOT_F].present) return solve_impl(h, rq, out);
     HIP_TRY(hipSetDevice(h->device));
     int rc;
     if ((rc = upload_program(h)) != WOST_OK) return rc;
-    if (mode_tree(mode) && (rc = ensure_tree(h)) != WOST_OK) return rc;
+    if (t.tree && (rc = ensure_tree(h)) != WOST_OK) return rc;
     KernelShape ks;
-    if ((rc = first_kernel_shape(h, mode, n_points, &ks)) != WOST_OK) return rc;
+    if ((rc = first_kernel_shape(h, t, &ks)) != WOST_OK) return rc;
     JitTicket ticket;
-    if (jit_kernel_try(h, mode, ks.block, ks.gpoly, ks.stage(), &ticket) != JitTry::kStarted)
+    if (jit_kernel_try(h, kernel_variant(h, t, ks, false, 1), &ticket) != JitTry::kStarted)
         return solve_impl(h, rq, out);
 
     const int64_t max_piece = kMaxBatchWalks / WOST_BLOCK_WALKS * WOST_BLOCK_WALKS;   // walks of a point per launch
@@ -1979,16 +1964,16 @@ int wost_prepare_sources(wost_handle* h, const wost_field* const* sources, int32
         return fail(WOST_ERR_UNSUPPORTED, "multi-source solves need the field-specialised kernel (disabled by wost_set_jit)");
     Program prog;
     build_program(f.data(), h->sigma_bar, prog);
-    const int mode = walk_mode_src(h, f[SLOT_F].present);
+    const WalkTraits t = walk_traits(h, f[SLOT_F].present);
     HIP_TRY(hipSetDevice(h->device));
-    if (mode_tree(mode)) {   // the staging choice depends on the tree's size
+    if (t.tree) {   // the staging choice depends on the tree's size
         std::lock_guard<std::mutex> lock(g_prepare_mu);
         if ((rc = ensure_tree(h)) != WOST_OK) return rc;
     }
     KernelShape ks;
-    if ((rc = first_kernel_shape(h, mode, n_points, &ks)) != WOST_OK) return rc;
+    if ((rc = first_kernel_shape(h, t, &ks)) != WOST_OK) return rc;
     std::string src, err;
-    if ((rc = jit_source(h, prog, mode, false, n, ks.block, ks.gpoly, ks.stage(), &src)) != WOST_OK) return rc;
+    if ((rc = jit_source(h, prog, kernel_variant(h, t, ks, false, n), nullptr, &src)) != WOST_OK) return rc;
     hipFunction_t fn = nullptr;
     if (!jit_get_kernel(h->opt, h->device, src, &fn, &err, nullptr, nullptr))
         return fail(WOST_ERR_UNSUPPORTED, "field-specialised kernel unavailable: %s", err.c_str());
@@ -2068,7 +2053,7 @@ int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources,
         ns = n_sources;
     }
     build_program(h->fields, h->sigma_bar, h->prog);
-    const int mode = walk_mode(h);
+    const WalkTraits t = walk_traits(h);
     // no device here: the segment angles of a compiled-in Neumann polyline come from the
     // host's atan2f (the kernels use the device's bits; this source is for offline study)
     const int nn = (int)(h->nverts.size() / 2);
@@ -2078,21 +2063,21 @@ int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources,
         const float2 n = segment_left_normal(a, b);
         phi[i] = std::atan2(n.y, n.x);
     }
+    // the first solve's kernel without a device: 256 threads, nothing of the tree staged
+    KernelVariant v = kernel_variant(h, t, KernelShape{}, false, ns);
     // study builds: offline study of the tree kernels' LDS staging (tools/jit_isa.py --stage):
     // the source of staging level WOST_KERNEL_SOURCE_STAGE (2: records and vertices, 1:
-    // records, with the tree_lds_block workgroup) instead of the 256-thread unstaged kernel
-    int stage = 0, block = kWalkBlock;
+    // records, with the tree_lds_block workgroup) instead
 #if defined(WOST_STUDY)
-    if (const char* e = std::getenv("WOST_KERNEL_SOURCE_STAGE"); e && mode_tree(mode)) {
-        stage = std::max(0, std::min(2, std::atoi(e)));
-        block = stage == 2 ? kTreeStageVertsBlock : stage == 1 ? h->opt.tree_lds_block : kWalkBlock;
+    if (const char* e = std::getenv("WOST_KERNEL_SOURCE_STAGE"); e && t.tree) {
+        v.tree_stage = std::max(0, std::min(2, std::atoi(e)));
+        v.block = v.tree_stage == 2 ? kTreeStageVertsBlock : v.tree_stage == 1 ? h->opt.tree_lds_block : kWalkBlock;
     }
 #endif
-    const std::string src = jit_generate(h->opt, mode, *h->prog.hdr(), h->prog.terms(), h->prog.factors(), h->dverts.data(),
-                                         (int)(h->dverts.size() / 2), h->nverts.data(), nn, false, ns, block,
-                                         phi.empty() ? nullptr : phi.data(), false, stage, exact_trig_of(h),
-                                         mode_delta(mode) ? n_wavenumbers : 0, n_charges);
+    std::string src;
+    rc = jit_source(h, h->prog, v, phi.empty() ? nullptr : phi.data(), &src);
     delete h;
+    if (rc != WOST_OK) return rc;
     *length = (int64_t)src.size();
     if (out && capacity > 0) {
         const size_t n = std::min<size_t>(src.size(), (size_t)capacity - 1);
@@ -2258,7 +2243,7 @@ int wost_set_trig(wost_handle* h, int32_t mode) {
         return fail(WOST_ERR_INVALID_ARG, "trig mode must be WOST_TRIG_AUTO, _EXACT or _FAST");
     h->trig_mode = mode;
     h->jit_fn = nullptr;
-    h->jit_mode = -1;
+    h->jit_variant.reset();
     return WOST_OK;
 }
 
@@ -2272,7 +2257,7 @@ int wost_set_jit(wost_handle* h, int32_t enable) {
     if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
     h->jit_enabled = enable != 0;
     h->jit_fn = nullptr;
-    h->jit_mode = -1;
+    h->jit_variant.reset();
     return WOST_OK;
 }
 
@@ -2286,7 +2271,7 @@ int wost_set_option(wost_handle* h, const char* name, double value) {
         return fail(WOST_ERR_UNSUPPORTED, "option \"%s\" exists in study builds only (make study)", name);
     if (kernel) {   // the generated source changes: rebuild the handle's kernel
         h->jit_fn = nullptr;
-        h->jit_mode = -1;
+        h->jit_variant.reset();
     }
     return WOST_OK;
 }

@@ -697,24 +697,25 @@ void jit_start_identity_probe() {
 
 bool jit_const_dirichlet(const Options& o, int nd) { return nd <= o.const_vertices; }
 
-bool jit_const_neumann(const Options& o, int mode, int nn) {
-    return mode_neu(mode) && !mode_tree(mode) && nn >= 1 && nn <= o.const_vertices;
+bool jit_const_neumann(const Options& o, const WalkTraits& t, int nn) {
+    return t.neu && !t.tree && nn >= 1 && nn <= o.const_vertices;
 }
 
-bool jit_fused_neumann_scan(const Options& o, int mode, int nn) {
+bool jit_fused_neumann_scan(const Options& o, const WalkTraits& t, int nn) {
     // (Options::fused_scan = 0: the two separate scans, the round-4 kernel; same bits)
-    return mode_neu(mode) && !mode_tree(mode) && !mode_fix(mode) && !jit_const_neumann(o, mode, nn) && nn >= 66 &&
-           o.fused_scan != 0;
+    return t.neu && !t.tree && !t.fix && !jit_const_neumann(o, t, nn) && nn >= 66 && o.fused_scan != 0;
 }
 
-std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, const DTerm* terms, const DFactor* factors,
-                         const float* dverts, int nd, const float* nverts, int nn, bool record, int n_sources,
-                         int block, const float* seg_phi, bool global_polylines, int tree_stage,
-                         bool exact_trig, int n_wavenumbers, int n_charges) {
-    const bool neu = mode_neu(mode);
-    const bool src = mode_src(mode);
-    const bool delta = mode_delta(mode);
-    const bool tree = mode_tree(mode);
+std::string jit_generate(const Options& opt, const KernelVariant& v, const ProgramView& prog, const PolylineView& poly) {
+    const WalkTraits& t = v.traits;
+    const bool neu = t.neu, src = t.src, delta = t.delta, tree = t.tree;
+    const DProgram& hdr = *prog.hdr;
+    const DTerm* const terms = prog.terms;
+    const DFactor* const factors = prog.factors;
+    const float* const dverts = poly.dverts;
+    const float* const nverts = poly.nverts;
+    const float* const seg_phi = poly.seg_phi;
+    const int nd = poly.nd, nn = poly.nn;
     const DField& fG = hdr.field[SLOT_G];
     const DField& fF = hdr.field[SLOT_F];
     const DField& fS = hdr.field[SLOT_SIGMA];
@@ -733,9 +734,9 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
     if (xf & (1 << 29)) o << "#define WOST_EXP_UNIT_TAB 1\n";   // A/B: unit_direction's (n, y) table
     if (xf & 131072) o << "#define WOST_EXP_SCAN_BITS 1\n";   // A/B: neumann_scan_both's per-vertex bits
     if ((xf >> 18) & 1023) o << "#define WOST_ABL_DUP " << ((xf >> 18) & 1023) << "\n";   // phase_dup.sh
-    o << "#define WOST_JIT_TRIG_EXACT " << (exact_trig ? 1 : 0) << "\n";   // wost_set_trig
+    o << "#define WOST_JIT_TRIG_EXACT " << (v.exact_trig ? 1 : 0) << "\n";   // wost_set_trig
     // wavenumbers set (wost_set_wavenumbers): the collision weight reads WalkArgs::k2
-    if (n_wavenumbers >= 1) o << "#define WOST_WAVENUMBERS 1\n";
+    if (v.n_wavenumbers >= 1) o << "#define WOST_WAVENUMBERS 1\n";
     if (xf & 2048) o << "#define WOST_EXP_IEEE_SQRT 1\n";
     // the handle's bit-preserving kernel options (wost_set_option; -1: the kernel's default)
     if (opt.philox_ahead >= 0) o << "#define WOST_PHILOX_AHEAD " << opt.philox_ahead << "\n";
@@ -745,12 +746,12 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
     if (opt.pool_min_push != 1) o << "#define WOST_POOL_MIN_PUSH " << opt.pool_min_push << "\n";
     if (opt.tree_iter_stats && tree) o << "#define WOST_TREE_ITER_STATS 1\n";   // study builds: loop counters
     if (opt.vote_stats) o << "#define WOST_VOTE_STATS 1\n";                      // study builds: vote counters
-    if (tree && tree_stage >= 1) o << "#define WOST_TREE_STAGED 1\n";    // every record in LDS
-    if (tree && tree_stage >= 2) o << "#define WOST_TREE_VSTAGED 1\n";   // and the Neumann vertices
+    if (tree && v.tree_stage >= 1) o << "#define WOST_TREE_STAGED 1\n";    // every record in LDS
+    if (tree && v.tree_stage >= 2) o << "#define WOST_TREE_VSTAGED 1\n";   // and the Neumann vertices
     if (opt.tree_qmargin >= 0) o << "#define WOST_TREE_QMARGIN " << opt.tree_qmargin << "\n";
     if (opt.tree_share_min >= 1) o << "#define WOST_TREE_SHARE_MIN " << opt.tree_share_min << "\n";
     if (opt.tree_batch >= 1) o << "#define WOST_TREE_BATCH " << (opt.tree_batch >= 4 ? 4 : opt.tree_batch >= 2 ? 2 : 1) << "\n";
-    o << "// generated by libwost (wost_jit.cpp): walk kernel, mode " << mode << "\n"
+    o << "// generated by libwost (wost_jit.cpp): walk kernel, " << traits_name(t) << "\n"
       << "#include \"wost_walk.h\"\n\nnamespace {\nstruct GenFields {\n"
       << "    const float* grid;   // tabulated field values (WOST_FK_GRID) in the program buffer\n"
       << "    const char* pb;      // the program buffer (multi-source kernels read the sources' parameters)\n"
@@ -761,8 +762,8 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
       << (fG.present ? value_body(fG, terms, factors) : "        return 0.0f;\n") << "    }\n";
     // (a multi-source kernel never calls f(): its walks score the sources through f_multi)
     o << "    __device__ __forceinline__ float f(float x, float y) const {\n"
-      << (fF.present && n_sources == 1 ? value_body(fF, terms, factors) : "        return 0.0f;\n") << "    }\n";
-    if (n_sources > 1) {   // multi-source: every source's value, each with f()'s operation sequence
+      << (fF.present && v.n_sources == 1 ? value_body(fF, terms, factors) : "        return 0.0f;\n") << "    }\n";
+    if (v.n_sources > 1) {   // multi-source: every source's value, each with f()'s operation sequence
         o << "    __device__ __forceinline__ void f_multi(float x, float y, float* out) const {\n";
         std::vector<int> canon(hdr.n_factors_total);   // (value_body_param)
         for (int j = 0; j < hdr.n_factors_total; ++j) {
@@ -773,7 +774,7 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
                     break;
                 }
         }
-        for (int s = 0; s < n_sources; ++s) {
+        for (int s = 0; s < v.n_sources; ++s) {
             const DField& fs = hdr.field[s == 0 ? SLOT_F : SLOT_EXTRA + s - 1];
             o << "        out[" << s << "] = [&]() {\n"
               << (!fs.present          ? std::string("        return 0.0f;\n")
@@ -799,20 +800,20 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
     // vectors and squared lengths fold to constants (the same IEEE operations)
     const bool dconst = jit_const_dirichlet(opt, nd);
     // a compiled-in Neumann polyline also needs its segment angles as constants
-    const bool nconst = jit_const_neumann(opt, mode, nn) && (seg_phi != nullptr || nn < 2);
+    const bool nconst = jit_const_neumann(opt, t, nn) && (seg_phi != nullptr || nn < 2);
     o << "    static constexpr bool kConstDirichlet = " << (dconst ? "true" : "false") << ";\n";
     o << "    static constexpr bool kConstNeumann = " << (nconst ? "true" : "false") << ";\n";
     // a long Neumann polyline scanned (no segment tree: the brute-force kernel): both
     // queries in one pass with the per-vertex line filter (neumann_scan_both);
     // Options::fused_scan = 0: the two separate scans instead (A/B)
-    const bool fused = !nconst && jit_fused_neumann_scan(opt, mode, nn);
+    const bool fused = !nconst && jit_fused_neumann_scan(opt, t, nn);
     o << "    static constexpr bool kFusedNeumann = " << (fused ? "true" : "false") << ";\n";
     if (fused) {
         float c1 = 0.0f;
         for (int i = 0; i < nn; ++i) c1 = std::max(c1, std::fabs(nverts[2 * i]) + std::fabs(nverts[2 * i + 1]));
         o << "    __device__ __forceinline__ wost::ScanBoth neumann_scan_both(const float2* sN, int nn, float x, float y,"
              " float dx, float dy) const {\n"
-          << "        return wost::neumann_scan_both<" << (global_polylines ? "true" : "false") << ">(sN, nn, "
+          << "        return wost::neumann_scan_both<" << (v.global_polylines ? "true" : "false") << ">(sN, nn, "
           << lit(c1 * 1.0001f) << ", x, y, dx, dy);\n    }\n";
     } else {
         o << "    __device__ __forceinline__ wost::ScanBoth neumann_scan_both(const float2*, int, float, float, float,"
@@ -897,20 +898,20 @@ std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, cons
     // the cooperative tree kernels, whose record visits load four children's words at
     // once (profiles/r03_tree/tree_batch_waves_ab.log), 4 when the tree's records are
     // staged (one 16-wave or two 8-wave workgroups per CU)
-    int waves = tree ? (block != kWalkBlock ? 4 : 5) : 7;
+    int waves = tree ? (v.block != kWalkBlock ? 4 : 5) : 7;
     if (opt.jit_waves > 0) waves = opt.jit_waves;
-    o << "extern \"C\" __global__ void __launch_bounds__(" << block << ", " << waves << ")\n"
+    o << "extern \"C\" __global__ void __launch_bounds__(" << v.block << ", " << waves << ")\n"
       << "wost_walk_jit(const wost::WalkArgs A) {\n"
       << "    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];\n"
       << "    const GenFields fld{reinterpret_cast<const float*>(A.prog + "
       << program_grid_offset(hdr.n_terms_total, hdr.n_factors_total) << "ull), A.prog};\n"
       << "    wost::walk_body<" << (neu ? "true" : "false") << ", " << (src ? "true" : "false") << ", "
-      << (delta ? "true" : "false") << ", " << (tree ? "true" : "false") << ", " << (record ? "true" : "false")
-      << ", " << n_sources << ", " << (mode_fix(mode) ? "true" : "false") << ", "
-      << (global_polylines ? "true" : "false");
+      << (delta ? "true" : "false") << ", " << (tree ? "true" : "false") << ", " << (v.record ? "true" : "false")
+      << ", " << v.n_sources << ", " << (t.fix ? "true" : "false") << ", "
+      << (v.global_polylines ? "true" : "false");
     // NK (a handle without wavenumbers: its kernel as ever), then PC (likewise without point charges)
-    if (n_wavenumbers >= 1 || n_charges >= 1) o << ", " << std::max(n_wavenumbers, 1);
-    if (n_charges >= 1) o << ", " << n_charges;
+    if (v.n_wavenumbers >= 1 || v.n_charges >= 1) o << ", " << std::max(v.n_wavenumbers, 1);
+    if (v.n_charges >= 1) o << ", " << v.n_charges;
     o << ">(A, fld, smem);\n}\n";
     if (delta)   // alpha at the query points, with these fields (WalkArgs::point_alpha)
         o << "extern \"C\" __global__ void __launch_bounds__(256)\n"

@@ -17,41 +17,42 @@
 
 #include "wost_device.h"
 #include "wost_options.h"
+#include "wost_variant.h"
 
 namespace wost {
 
-// Which polylines a specialised kernel of `mode` compiles in (at most
-// Options::const_vertices vertices, default kJitMaxConstVertices; they are then not
-// staged in LDS).
+// Which polylines a specialised kernel with traits `t` compiles in (at most
+// Options::const_vertices vertices, default kJitMaxConstVertices; a compiled-in
+// Dirichlet polyline is not staged in LDS).
 bool jit_const_dirichlet(const Options& o, int nd);
-bool jit_const_neumann(const Options& o, int mode, int nn);
+bool jit_const_neumann(const Options& o, const WalkTraits& t, int nn);
 // a long Neumann polyline scanned without the segment tree (the brute-force kernel, reference
 // mode): both queries of a step in one pass (wost_device.h neumann_scan_both)
-bool jit_fused_neumann_scan(const Options& o, int mode, int nn);
+bool jit_fused_neumann_scan(const Options& o, const WalkTraits& t, int nn);
 
-// HIP source of a walk kernel named "wost_walk_jit" for walk mode `mode`
-// (wost_internal.h WalkMode) with the fields of `prog` and short polylines
-// (Dirichlet dverts[2*nd], Neumann nverts[2*nn]) compiled in; `record`: the
-// kernel can record walks (return_history); `n_sources` > 1: the walk scores
-// sources SLOT_F, SLOT_EXTRA.. (multi-source batching).
-// `block`: threads per workgroup the kernel is launched with; seg_phi: the
-// device's per-segment normal angles of a compiled-in Neumann polyline (nn - 1
-// floats, read back from the setup kernel so the constants carry its bits);
-// global_polylines: the kernel reads polylines that are not compiled in from
-// global memory instead of staging them in LDS (wost_walk.h GL). tree_stage (tree
-// modes): 0 = the segment tree through L1/L2, 1 = its records staged in LDS
-// (WOST_TREE_STAGED), 2 = its records and the Neumann vertices (WOST_TREE_VSTAGED) --
-// the caller's staging decision, independent of the workgroup size.
+// The fields a kernel compiles in: the program's header, terms and factors.
+struct ProgramView {
+    const DProgram* hdr;
+    const DTerm* terms;
+    const DFactor* factors;
+};
+// The polylines (Dirichlet dverts[2*nd], Neumann nverts[2*nn]; short ones are compiled in)
+// and seg_phi: the device's per-segment normal angles of a compiled-in Neumann polyline
+// (nn - 1 floats, read back from the setup kernel so the constants carry its bits), or null.
+struct PolylineView {
+    const float* dverts;
+    int nd;
+    const float* nverts;
+    int nn;
+    const float* seg_phi;
+};
+
+// HIP source of the walk kernel named "wost_walk_jit" for the variant `v` (wost_variant.h:
+// its traits, recorder, channel counts, workgroup, polyline placement, tree staging -- the
+// caller's decision, independent of the workgroup size -- and trig choice) with the fields
+// of `prog` and the short polylines of `poly` compiled in.
 // `opt`: the handle's kernel options (wost_options.h).
-// n_wavenumbers >= 1 (wost_set_wavenumbers): the walk carries that many attenuations and
-// reads their k^2 from WalkArgs::k2 at run time (wost_walk.h NK); 0: none set.
-// n_charges >= 1 (wost_set_point_sources): the walk scores that many point charges, read
-// from WalkArgs::charges at run time (wost_walk.h PC); 0: none set, the source as ever.
-std::string jit_generate(const Options& opt, int mode, const DProgram& hdr, const DTerm* terms, const DFactor* factors,
-                         const float* dverts, int nd, const float* nverts, int nn, bool record,
-                         int n_sources = 1, int block = 256, const float* seg_phi = nullptr,
-                         bool global_polylines = false, int tree_stage = 0, bool exact_trig = true,
-                         int n_wavenumbers = 0, int n_charges = 0);
+std::string jit_generate(const Options& opt, const KernelVariant& v, const ProgramView& prog, const PolylineView& poly);
 
 // Compiles (or fetches from the caches) the source for `device` and returns
 // the kernel. On failure returns false and a message in *err.

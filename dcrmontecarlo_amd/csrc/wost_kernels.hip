@@ -1,6 +1,6 @@
 // wost_kernels.hip -- precompiled gfx950 kernels of the Walk-on-Stars hot path.
 //
-// wost_walk_kernel<NEU,SRC,DELTA,TREE>: the walk loop of wost_walk.h with the
+// wost_walk_kernel<NEU,SRC,DELTA,TREE,FIX>: the walk loop of wost_walk.h with the
 // coefficient fields interpreted from a program buffer read through the
 // constant address space with uniform indices (scalar loads). wost_jit.cpp
 // builds the same loop with the fields compiled in.
@@ -154,46 +154,36 @@ hipError_t launch_point_alpha(const char* prog, const float2* pts, int64_t n, fl
     return hipGetLastError();
 }
 
-// mode -> kernel instantiation (MODE_* of wost_internal.h)
-#define WOST_FOR_MODE(mode, X)                                   \
-    switch (mode) {                                              \
-    case MODE_DIRICHLET: X(false, false, false, false, false);        \
-    case MODE_POISSON: X(false, true, false, false, false);           \
-    case MODE_MIXED: X(true, false, false, false, false);             \
-    case MODE_MIXED_POISSON: X(true, true, false, false, false);      \
-    case MODE_DELTA: X(false, true, true, false, false);              \
-    case MODE_MIXED_DELTA: X(true, true, true, false, false);         \
-    case MODE_MIXED_TREE: X(true, false, false, true, false);         \
-    case MODE_MIXED_POISSON_TREE: X(true, true, false, true, false);  \
-    case MODE_MIXED_DELTA_TREE: X(true, true, true, true, false);     \
-    case MODE_FIX_DIRICHLET: X(false, false, false, false, true);     \
-    case MODE_FIX_POISSON: X(false, true, false, false, true);        \
-    case MODE_FIX_MIXED: X(true, false, false, false, true);          \
-    case MODE_FIX_MIXED_POISSON: X(true, true, false, false, true);   \
-    case MODE_FIX_DELTA: X(false, true, true, false, true);           \
-    case MODE_FIX_MIXED_DELTA: X(true, true, true, false, true);      \
-    case MODE_FIX_MIXED_TREE: X(true, false, false, true, true);      \
-    case MODE_FIX_MIXED_POISSON_TREE: X(true, true, false, true, true); \
-    case MODE_FIX_MIXED_DELTA_TREE: X(true, true, true, true, true);  \
-    default: return hipErrorInvalidValue;                        \
-    }
+// traits -> kernel instantiation. The five booleans become template arguments one level at
+// a time; a kernel is instantiated for the valid combinations only (WalkTraits::valid), the
+// rest have none. (The kernels lie in the code object in the order of instantiation: fix
+// outermost, false before true.)
+using WalkKernel = void (*)(const WalkArgs);
 
-hipError_t walk_occupancy(int mode, int nd, int nn, int n_points, int* blocks_per_cu) {
-    (void)n_points;
-    const size_t lds = walk_lds_bytes(mode, nd, nn, n_points);
-#define OCC(n, s, d, t, x) \
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, wost_walk_kernel<n, s, d, t, x>, kWalkBlock, lds)
-    WOST_FOR_MODE(mode, OCC)
-#undef OCC
+template <bool FIX, bool TREE, bool DELTA, bool NEU, bool SRC>
+WalkKernel walk_kernel_of() {
+    if constexpr (WalkTraits{NEU, SRC, DELTA, TREE, FIX}.valid()) return wost_walk_kernel<NEU, SRC, DELTA, TREE, FIX>;
+    else return nullptr;
+}
+template <bool... B, class... Rest>
+WalkKernel walk_kernel_of(bool b, Rest... rest) {
+    return !b ? walk_kernel_of<B..., false>(rest...) : walk_kernel_of<B..., true>(rest...);
+}
+WalkKernel walk_kernel_of(const WalkTraits& t) { return walk_kernel_of<>(t.fix, t.tree, t.delta, t.neu, t.src); }
+
+// (the precompiled kernels stage both polylines and nothing of the tree, 256-thread workgroups)
+hipError_t walk_occupancy(const WalkTraits& t, int nd, int nn, int* blocks_per_cu) {
+    const WalkKernel k = walk_kernel_of(t);
+    if (!k) return hipErrorInvalidValue;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, kWalkBlock,
+                                                        walk_lds_bytes({.traits = t, .nd = nd, .nn = nn}));
 }
 
-hipError_t launch_walk(int mode, const WalkArgs& a, int grid, hipStream_t s) {
-    const size_t lds = walk_lds_bytes(mode, a.nd, a.nn, a.n_points);
-#define LAUNCH(n, sr, d, t, x)                                       \
-    wost_walk_kernel<n, sr, d, t, x><<<grid, kWalkBlock, lds, s>>>(a); \
-    return hipGetLastError()
-    WOST_FOR_MODE(mode, LAUNCH)
-#undef LAUNCH
+hipError_t launch_walk(const WalkTraits& t, const WalkArgs& a, int grid, hipStream_t s) {
+    const WalkKernel k = walk_kernel_of(t);
+    if (!k) return hipErrorInvalidValue;
+    k<<<grid, kWalkBlock, walk_lds_bytes({.traits = t, .nd = a.nd, .nn = a.nn}), s>>>(a);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------

@@ -15,6 +15,9 @@
 #pragma once
 
 #include "wost_device.h"
+#if !defined(__HIPCC_RTC__)
+#include "wost_variant.h"   // (host side only: WalkLds below)
+#endif
 
 namespace wost {
 
@@ -276,28 +279,37 @@ constexpr size_t kTreeWaveScratchBytes = sizeof(TreeWaveScratch);
 //    word before the sampler's tail;
 //  * the sampler's nodes 1..N-1 (node 0 is a kernel argument);
 //  * the Dirichlet vertices, unless the Fields policy has them compiled in;
-//  * the Neumann vertices and segment angles (scan kernels), unless compiled in;
+//  * the Neumann vertices and segment angles (scan kernels), also when compiled in
+//    (walk_body kStageN);
 //  * with the segment tree, its first tree_lds records (128 B each), the tree_verts
 //    staged Neumann vertices, then one TreeWaveScratch per wave (the cooperative
 //    tree queries) of the `block`-thread workgroup.
 // Query points are read from global memory (once per walk, at refill).
-WOST_HD size_t walk_lds_bytes_for(bool neu, bool src, int nd, int nn, int n_points, bool tree = false,
-                                  bool delta = false, int tree_lds = 0, bool const_d = false, bool const_n = false,
-                                  bool global_polylines = false, int block = kWalkBlock, int tree_verts = 0) {
-    if (global_polylines) const_d = const_n = true;   // nothing of the polylines is staged
-    (void)n_points;
+#if !defined(__HIPCC_RTC__)   // the host sizes the launch; a run-time-compiled source never does
+struct WalkLds {
+    WalkTraits traits;
+    int nd = 0, nn = 0;              // vertex counts
+    int tree_lds = 0;                // records of the segment tree staged
+    int tree_verts = 0;              // Neumann vertices staged after them
+    bool const_d = false;            // the Dirichlet polyline is compiled in (field-specialised kernels)
+    bool global_polylines = false;   // nothing of the polylines is staged (wost_walk.h GL)
+    int block = kWalkBlock;          // threads per workgroup
+};
+WOST_HD size_t walk_lds_bytes(const WalkLds& k) {
+    const WalkTraits& t = k.traits;
     size_t b = 0;
-    if (src) b += delta ? sizeof(float4) * (size_t)kGnormCells : 16;
-    if (src) b += sizeof(float) * (size_t)kSamplerTailFloats;
+    if (t.src) b += t.delta ? sizeof(float4) * (size_t)kGnormCells : 16;
+    if (t.src) b += sizeof(float) * (size_t)kSamplerTailFloats;
     b = align16(b);
-    if (!const_d) b += align16(sizeof(float2) * (size_t)nd);
-    if (neu && !tree && !const_n)
-        b += align16(sizeof(float2) * (size_t)nn) + align16(sizeof(float) * (size_t)(nn > 1 ? nn - 1 : 0));
-    if (tree)
-        b += 8 * sizeof(float4) * (size_t)tree_lds + align16(sizeof(float2) * (size_t)tree_verts) +
-             kTreeWaveScratchBytes * (size_t)((block + 63) / 64);
+    if (!k.const_d && !k.global_polylines) b += align16(sizeof(float2) * (size_t)k.nd);
+    if (t.neu && !t.tree && !k.global_polylines)
+        b += align16(sizeof(float2) * (size_t)k.nn) + align16(sizeof(float) * (size_t)(k.nn > 1 ? k.nn - 1 : 0));
+    if (t.tree)
+        b += 8 * sizeof(float4) * (size_t)k.tree_lds + align16(sizeof(float2) * (size_t)k.tree_verts) +
+             kTreeWaveScratchBytes * (size_t)((k.block + 63) / 64);
     return b;
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // Wave-cooperative segment-tree queries (TREE kernels; compat="fixed" too, its ray

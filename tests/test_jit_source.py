@@ -18,7 +18,7 @@ HIPRTC_OPTS = ["-O3", "-std=c++17", "-fhip-fp32-correctly-rounded-divide-sqrt", 
 
 def test_generated_sources_name_their_variant():
     src = S.dcr_dipole().kernel_source()
-    assert "walk kernel, mode 5" in src and "wost_walk_jit" in src
+    assert "walk kernel, neumann+source+delta" in src and "wost_walk_jit" in src
     assert "walk_body<true, true, true, false, false, 1, false, false>" in src
     assert "wost_point_alpha_jit" in src                    # alpha at the query points (delta)
     assert "const float2 v[5]" in src                       # the square compiled in
