@@ -55,6 +55,11 @@ class WostPointCharge(ctypes.Structure):
     _fields_ = [("x", c_float), ("y", c_float), ("strength", c_float), ("source", c_int32)]
 
 
+class WostModel(ctypes.Structure):
+    """include/wost.h wost_model: a (sigma, alpha) pair; a NULL field follows wost_problem's rules."""
+    _fields_ = [("sigma", POINTER(WostField)), ("alpha", POINTER(WostField))]
+
+
 class WostPolyline(ctypes.Structure):
     _fields_ = [("xy", POINTER(c_float)), ("n_vertices", c_int32)]
 
@@ -129,6 +134,11 @@ def _load():
         "wost_num_sources": (c_int32, [H, POINTER(c_int32)]),
         "wost_set_wavenumbers": (c_int32, [H, POINTER(c_double), c_int32]),
         "wost_num_channels": (c_int32, [H, POINTER(c_int32)]),
+        "wost_set_models": (c_int32, [H, POINTER(WostModel), c_int32]),
+        "wost_models_info": (c_int32, [H, POINTER(c_int32), POINTER(c_uint64)]),
+        "wost_kernel_source_models": (c_int32, [POINTER(WostProblem), POINTER(WostModel), c_int32,
+                                                POINTER(POINTER(WostField)), c_int32, c_int32, ctypes.c_char_p,
+                                                c_int64, POINTER(c_int64)]),
         "wost_set_point_sources": (c_int32, [H, POINTER(WostPointCharge), c_int32, c_int32]),
         "wost_point_sources_info": (c_int32, [H, POINTER(c_int32), POINTER(c_uint64)]),
         "wost_ball_greens": (c_int32, [c_double, POINTER(c_float), POINTER(c_float), c_int64, POINTER(c_float)]),

@@ -408,7 +408,7 @@ class Communicator:
 def _distributed_sums(solver, comm: Communicator, p: np.ndarray, nWalks: int, maxSteps: int, eps: float,
                       seed: int):
     n = p.shape[0]
-    ns = ctypes.c_int32(1)   # values per walk: sources x wavenumbers (rows of 2C+1)
+    ns = ctypes.c_int32(1)   # values per walk: models x wavenumbers x sources (rows of 2C+1)
     _lib.check(_lib.lib.wost_num_channels(solver._h, ctypes.byref(ns)), "wost_num_channels")
     sums = np.zeros((n, 2 * ns.value + 1), np.float64)
     t = _lib.WostDistTiming()

@@ -115,6 +115,10 @@ int convert_field(const wost_field* in, HostField& out, const char* name) {
 // Flattened program for the device (and for host-side evaluation).
 struct Program {
     std::vector<unsigned char> bytes;
+    // the (sigma, alpha) descriptors of models 1.. (wost_set_models, n >= 2): host only, read by
+    // the generator (wost_jit.h ProgramView::models); their terms, factors and grid values
+    // follow the N_FIELDS fields' in `bytes`
+    std::vector<DField> models;
     const DProgram* hdr() const { return reinterpret_cast<const DProgram*>(bytes.data()); }
     const DTerm* terms() const { return reinterpret_cast<const DTerm*>(bytes.data() + sizeof(DProgram)); }
     const DFactor* factors() const {
@@ -127,29 +131,32 @@ struct Program {
     }
 };
 
-// f: N_FIELDS fields (absent ones empty)
-void build_program(const HostField* f, double sigma_bar, Program& out) {
+// f: N_FIELDS fields (absent ones empty); extra: the model fields after them (Program::models)
+void build_program(const HostField* f, double sigma_bar, Program& out, const std::vector<HostField>* extra = nullptr) {
     DProgram hdr{};
     std::vector<DTerm> terms;
     std::vector<DFactor> factors;
     std::vector<float> grid;
-    for (int s = 0; s < N_FIELDS; ++s) {
-        hdr.field[s].present = f[s].present ? 1 : 0;
-        hdr.field[s].flags = f[s].flags;
-        hdr.field[s].first_term = (int)terms.size();
-        hdr.field[s].n_terms = (int)f[s].terms.size();
+    auto add = [&](const HostField& hf, DField& d_) {
+        d_.present = hf.present ? 1 : 0;
+        d_.flags = hf.flags;
+        d_.first_term = (int)terms.size();
+        d_.n_terms = (int)hf.terms.size();
         const int fbase = (int)factors.size();
         const float gbase = (float)grid.size();   // exact: < 2^24 per field, checked on input
-        for (DTerm t : f[s].terms) {
+        for (DTerm t : hf.terms) {
             t.first += fbase;
             terms.push_back(t);
         }
-        for (DFactor d : f[s].factors) {
+        for (DFactor d : hf.factors) {
             if (d.kind == WOST_FK_GRID) d.p[6] += gbase;
             factors.push_back(d);
         }
-        grid.insert(grid.end(), f[s].grid.begin(), f[s].grid.end());
-    }
+        grid.insert(grid.end(), hf.grid.begin(), hf.grid.end());
+    };
+    for (int s = 0; s < N_FIELDS; ++s) add(f[s], hdr.field[s]);
+    out.models.assign(extra ? extra->size() : 0, DField{});
+    for (size_t s = 0; s < out.models.size(); ++s) add((*extra)[s], out.models[s]);
     hdr.sigma_bar = (float)sigma_bar;
     hdr.sqrt_sigma_bar = (float)std::sqrt(sigma_bar > 0 ? sigma_bar : 0.0);
     hdr.inv_sigma_bar = sigma_bar > 0 ? (float)(1.0 / sigma_bar) : 0.f;
@@ -192,7 +199,16 @@ struct wost_handle {
     // scores channels() = max(1, n_wavenumbers) * n_sources values per walk
     int n_wavenumbers = 0;
     float k2[WOST_MAX_SOURCES] = {};
-    int channels() const { return (n_wavenumbers > 0 ? n_wavenumbers : 1) * n_sources; }
+    // conductivity models (wost_set_models): 0 = none set. Model 0's (sigma, alpha) sit in
+    // SLOT_SIGMA / SLOT_ALPHA (the problem's own are kept in own_fields meanwhile), models 1..
+    // in model_fields[2 (m - 1)], [2 (m - 1) + 1]
+    int n_models = 0;
+    std::vector<HostField> model_fields;
+    HostField own_fields[2];
+    uint64_t models_sum = 0;   // FNV-1a 64 of the converted model fields (0: none)
+    int channels() const {
+        return (n_models > 0 ? n_models : 1) * (n_wavenumbers > 0 ? n_wavenumbers : 1) * n_sources;
+    }
     // point sources (wost_set_point_sources): the charges (n_sources counts their source
     // channels then), the Neumann segment(s) each lies on ([2 n], -1: none) and their device
     // image (WalkArgs::charges, kChargeWords words)
@@ -282,7 +298,7 @@ constexpr int64_t kLstatsWords = 8;
 
 int upload_program(wost_handle* h) {
     if (!h->prog_dirty) return WOST_OK;
-    build_program(h->fields, h->sigma_bar, h->prog);
+    build_program(h->fields, h->sigma_bar, h->prog, &h->model_fields);
     if (h->prog.bytes.size() > h->d_prog_cap) {
         if (h->d_prog) (void)hipFree(h->d_prog);
         h->d_prog = nullptr;
@@ -315,7 +331,9 @@ int jit_source(const wost_handle* h, const Program& prog, const KernelVariant& v
         HIP_TRY(hipMemcpy(phi.data(), h->d_seg_phi, sizeof(float) * phi.size(), hipMemcpyDeviceToHost));
         seg_phi = phi.data();
     }
-    *src = jit_generate(h->opt, v, ProgramView{prog.hdr(), prog.terms(), prog.factors()},
+    *src = jit_generate(h->opt, v,
+                        ProgramView{prog.hdr(), prog.terms(), prog.factors(),
+                                    prog.models.empty() ? nullptr : prog.models.data()},
                         PolylineView{h->dverts.data(), (int)(h->dverts.size() / 2), h->nverts.data(), nn, seg_phi});
     return WOST_OK;
 }
@@ -982,7 +1000,8 @@ KernelVariant kernel_variant(const wost_handle* h, const WalkTraits& t, const Ke
                              int n_sources) {
     return KernelVariant{.traits = t, .record = record, .n_sources = n_sources,
                          .n_wavenumbers = t.delta ? h->n_wavenumbers : 0,   // (0: the kernel without the k2 read)
-                         .n_charges = (int)h->charges.size(), .block = ks.block, .global_polylines = ks.gpoly,
+                         .n_charges = (int)h->charges.size(), .n_models = t.delta ? h->n_models : 0,
+                         .block = ks.block, .global_polylines = ks.gpoly,
                          .tree_stage = ks.stage(), .exact_trig = exact_trig_of(h)};
 }
 
@@ -1053,7 +1072,7 @@ int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, i
                             h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
             if (ns > 1)
                 return fail(WOST_ERR_UNSUPPORTED,
-                            "multi-source and multi-wavenumber solves need the field-specialised kernel%s%s",
+                            "multi-source, multi-wavenumber and multi-model solves need the field-specialised kernel%s%s",
                             h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
             ks.block = kWalkBlock;
             ks.tree_lds = ks.tree_verts = 0;
@@ -1094,7 +1113,10 @@ int check_request(const wost_handle* h, const SolveRequest& rq, SolveRanges* ran
     if (ns != 1 && !rq.multi)
         return fail(WOST_ERR_INVALID_ARG,
                     "the handle scores %d channels (%d sources of wost_set_sources x %d wavenumbers of "
-                    "wost_set_wavenumbers): use wost_solve_multi", ns, n_src, ns / n_src);
+                    "wost_set_wavenumbers x %d models of wost_set_models): use wost_solve_multi", ns, n_src,
+                    std::max(h->n_wavenumbers, 1), std::max(h->n_models, 1));
+    if (h->n_models > 1 && n_points > INT32_MAX)
+        return fail(WOST_ERR_INVALID_ARG, "model batching takes at most 2^31 - 1 query points per solve");
     if (n_points < 0 || (n_points > 0 && !points)) return fail(WOST_ERR_INVALID_ARG, "bad points");
     if (W <= 0) return fail(WOST_ERR_INVALID_ARG, "nWalks must be >= 1 (got %lld)", (long long)W);
     if (rq.max_steps < 0) return fail(WOST_ERR_INVALID_ARG, "maxSteps must be >= 0");
@@ -1219,7 +1241,8 @@ WalkArgs fill_walk_args(const wost_handle* h, const SolveRequest& rq, const Walk
 // (a parked walk holds one attenuation: launches of several wavenumbers run without pools)
 int setup_pools(wost_handle* h, const WalkTraits& t, int n_src, int blocks_per_cu, WalkArgs* a) {
     const Options& O = h->opt;
-    if (!t.tree || O.tree_pool == 0 || h->nverts.size() < 4 || h->n_wavenumbers > 1 || !h->charges.empty())
+    if (!t.tree || O.tree_pool == 0 || h->nverts.size() < 4 || h->n_wavenumbers > 1 || !h->charges.empty() ||
+        h->n_models > 1)
         return WOST_OK;
     float x0 = h->nverts[0], x1 = x0, y0 = h->nverts[1], y1 = y0;
     for (size_t i = 2; i + 1 < h->nverts.size(); i += 2) {
@@ -1243,7 +1266,9 @@ int setup_pools(wost_handle* h, const WalkTraits& t, int n_src, int blocks_per_c
 // Delta tracking: alpha at the query points, with the walk kernel's fields.
 int launch_point_alpha_for(wost_handle* h, const WalkTraits& t, hipFunction_t jfn, int64_t n_points, WalkArgs* a) {
     if (!t.delta || n_points <= 0) return WOST_OK;
-    if (int rc = ensure_cap(h->d_point_alpha, h->point_alpha_cap, n_points)) return rc;
+    // (a model-batched kernel's wost_point_alpha_jit writes every model's: [models][n_points])
+    const int64_t nm = jfn && h->n_models > 1 ? h->n_models : 1;
+    if (int rc = ensure_cap(h->d_point_alpha, h->point_alpha_cap, nm * n_points)) return rc;
     if (jfn) {
         const float2* pts = h->d_points;
         long long n = (long long)n_points;
@@ -1845,6 +1870,7 @@ int fields_with_sources(const wost_handle* h, const wost_field* const* sources, 
     }
     for (int s = 0; s < N_SLOTS; ++s)
         if (s != SLOT_F) grid += (int64_t)h->fields[s].grid.size();
+    for (const HostField& mf : h->model_fields) grid += (int64_t)mf.grid.size();
     if (grid >= (int64_t(1) << 24))
         return fail(WOST_ERR_INVALID_ARG, "tabulated fields hold %lld values together (limit 2^24)", (long long)grid);
     for (int s = 0; s < N_FIELDS; ++s) out[s] = h->fields[s];
@@ -1939,9 +1965,9 @@ int wost_set_sources(wost_handle* h, const wost_field* const* sources, int32_t n
     std::vector<HostField> f(N_FIELDS);
     int rc = fields_with_sources(h, sources, n, f.data());
     if (rc != WOST_OK) return rc;
-    if (h->n_wavenumbers > 0 && n * h->n_wavenumbers > WOST_MAX_SOURCES)
-        return fail(WOST_ERR_INVALID_ARG, "%d sources x %d wavenumbers exceed %d channels", n, h->n_wavenumbers,
-                    WOST_MAX_SOURCES);
+    if ((int64_t)n * std::max(h->n_wavenumbers, 1) * std::max(h->n_models, 1) > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "%d sources x %d wavenumbers x %d models exceed %d channels", n,
+                    std::max(h->n_wavenumbers, 1), std::max(h->n_models, 1), WOST_MAX_SOURCES);
     for (int s = 0; s < N_FIELDS; ++s) h->fields[s] = std::move(f[s]);
     h->n_sources = n;
     h->prog_dirty = true;
@@ -1957,13 +1983,13 @@ int wost_prepare_sources(wost_handle* h, const wost_field* const* sources, int32
     std::vector<HostField> f(N_FIELDS);
     int rc = fields_with_sources(h, sources, n, f.data());
     if (rc != WOST_OK) return rc;
-    if (h->n_wavenumbers > 0 && n * h->n_wavenumbers > WOST_MAX_SOURCES)
-        return fail(WOST_ERR_INVALID_ARG, "%d sources x %d wavenumbers exceed %d channels", n, h->n_wavenumbers,
-                    WOST_MAX_SOURCES);
+    if ((int64_t)n * std::max(h->n_wavenumbers, 1) * std::max(h->n_models, 1) > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "%d sources x %d wavenumbers x %d models exceed %d channels", n,
+                    std::max(h->n_wavenumbers, 1), std::max(h->n_models, 1), WOST_MAX_SOURCES);
     if (!h->jit_enabled)
         return fail(WOST_ERR_UNSUPPORTED, "multi-source solves need the field-specialised kernel (disabled by wost_set_jit)");
     Program prog;
-    build_program(f.data(), h->sigma_bar, prog);
+    build_program(f.data(), h->sigma_bar, prog, &h->model_fields);
     const WalkTraits t = walk_traits(h, f[SLOT_F].present);
     HIP_TRY(hipSetDevice(h->device));
     if (t.tree) {   // the staging choice depends on the tree's size
@@ -1983,6 +2009,99 @@ int wost_prepare_sources(wost_handle* h, const wost_field* const* sources, int32
 }  // extern "C"
 
 namespace {
+// ---- conductivity models (wost_set_models, wost_kernel_source_models) ----
+
+// models[0..n) converted with wost_problem's NULL rules (sigma NULL: 0; alpha NULL: the
+// detached constant 1, as create_host): out[2 m] sigma, out[2 m + 1] alpha.
+int convert_models(const wost_model* models, int32_t n, std::vector<HostField>* out) {
+    out->assign(2 * (size_t)n, HostField());
+    for (int m = 0; m < n; ++m) {
+        if (!models[m].sigma && !models[m].alpha)
+            return fail(WOST_ERR_INVALID_ARG, "model %d has neither sigma nor alpha", m);
+        char name[40];
+        HostField& sg = (*out)[2 * (size_t)m];
+        HostField& al = (*out)[2 * (size_t)m + 1];
+        std::snprintf(name, sizeof(name), "models[%d].sigma", m);
+        if (int rc = convert_field(models[m].sigma, sg, name)) return rc;
+        std::snprintf(name, sizeof(name), "models[%d].alpha", m);
+        if (int rc = convert_field(models[m].alpha, al, name)) return rc;
+        if (!al.present) {
+            al.present = true;
+            al.flags = WOST_FIELD_DETACHED;
+            al.terms.push_back(DTerm{1.0f, 0, 0, 0});
+        }
+        if (!sg.present) {
+            sg.present = true;
+            sg.terms.push_back(DTerm{0.0f, 0, 0, 0});
+        }
+    }
+    return WOST_OK;
+}
+
+// FNV-1a 64 of the converted fields: the count, then per field its flags, terms (coef,
+// first, nf), factors (kind, p) and grid values. Padding never enters.
+uint64_t models_checksum(const std::vector<HostField>& f) {
+    if (f.empty()) return 0;
+    uint64_t hsh = 1469598103934665603ull;
+    auto eat = [&](const void* p, size_t n) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        for (size_t i = 0; i < n; ++i) hsh = (hsh ^ b[i]) * 1099511628211ull;
+    };
+    const int32_t n = (int32_t)(f.size() / 2);
+    eat(&n, sizeof(n));
+    for (const HostField& hf : f) {
+        const int32_t head[4] = {hf.flags, (int32_t)hf.terms.size(), (int32_t)hf.factors.size(), (int32_t)hf.grid.size()};
+        eat(head, sizeof(head));
+        for (const DTerm& t : hf.terms) { eat(&t.coef, 4); eat(&t.first, 4); eat(&t.nf, 4); }
+        for (const DFactor& d : hf.factors) { eat(&d.kind, 4); eat(d.p, sizeof(d.p)); }
+        if (!hf.grid.empty()) eat(hf.grid.data(), sizeof(float) * hf.grid.size());
+    }
+    return hsh;
+}
+
+// The checks a model set must pass on this handle (no device).
+int check_models(const wost_handle* h, int32_t n, const std::vector<HostField>& conv) {
+    if (!h->delta)
+        return fail(WOST_ERR_UNSUPPORTED,
+                    "models need delta tracking (the conductivity enters through the walk's weights only there): "
+                    "create the solver with sigma or alpha");
+    if ((int64_t)n * std::max(h->n_wavenumbers, 1) * h->n_sources > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "%d models x %d wavenumbers x %d sources exceed %d channels", n,
+                    std::max(h->n_wavenumbers, 1), h->n_sources, WOST_MAX_SOURCES);
+    if (n >= 2 && !h->charges.empty())
+        return fail(WOST_ERR_UNSUPPORTED, "several models cannot be combined with point sources (the charge buffer "
+                                          "holds one alpha per charge): clear them first");
+    int64_t grid = 0;
+    for (const HostField& hf : conv) grid += (int64_t)hf.grid.size();
+    for (int s = 0; s < N_FIELDS; ++s)
+        if (s != SLOT_SIGMA && s != SLOT_ALPHA) grid += (int64_t)h->fields[s].grid.size();
+    if (grid >= (int64_t(1) << 24))
+        return fail(WOST_ERR_INVALID_ARG, "tabulated fields hold %lld values together (limit 2^24)", (long long)grid);
+    return WOST_OK;
+}
+
+// Puts the converted models (2 n fields; n = 0: none) into the handle: model 0 into the
+// program's SLOT_SIGMA / SLOT_ALPHA, the rest after the extra sources.
+void install_models(wost_handle* h, int32_t n, std::vector<HostField>& conv) {
+    if (h->n_models == 0) {   // keep the problem's own pair
+        h->own_fields[0] = h->fields[SLOT_SIGMA];
+        h->own_fields[1] = h->fields[SLOT_ALPHA];
+    }
+    if (n == 0) {
+        h->fields[SLOT_SIGMA] = h->own_fields[0];
+        h->fields[SLOT_ALPHA] = h->own_fields[1];
+        h->model_fields.clear();
+        h->models_sum = 0;
+    } else {
+        h->models_sum = models_checksum(conv);
+        h->fields[SLOT_SIGMA] = std::move(conv[0]);
+        h->fields[SLOT_ALPHA] = std::move(conv[1]);
+        h->model_fields.assign(std::make_move_iterator(conv.begin() + 2), std::make_move_iterator(conv.end()));
+    }
+    h->n_models = n;
+    h->prog_dirty = true;
+}
+
 // wost_set_point_sources' argument checks (shared with wost_kernel_source_points, which has
 // counts only: charges == nullptr skips the per-charge checks).
 int check_point_sources(const wost_handle* h, const wost_point_charge* charges, int32_t n, int32_t n_sources) {
@@ -1995,6 +2114,9 @@ int check_point_sources(const wost_handle* h, const wost_point_charge* charges, 
     if (n_sources < 1 || n_sources > n)
         return fail(WOST_ERR_INVALID_ARG, "need 1 <= n_sources <= n (every source has a charge), got %d sources of %d "
                                           "charges", n_sources, n);
+    if (h->n_models >= 2)
+        return fail(WOST_ERR_UNSUPPORTED, "point sources cannot be combined with several models (wost_set_models; the "
+                                          "charge buffer holds one alpha per charge): clear the models first");
     const int nk = h->n_wavenumbers > 0 ? h->n_wavenumbers : 1;
     if ((int64_t)n_sources * nk > WOST_MAX_SOURCES)
         return fail(WOST_ERR_INVALID_ARG, "%d sources x %d wavenumbers exceed %d channels", n_sources, nk, WOST_MAX_SOURCES);
@@ -2019,8 +2141,11 @@ int check_point_sources(const wost_handle* h, const wost_point_charge* charges, 
 // wost_kernel_source_channels, and with n_charges > 0 wost_kernel_source_points (n_sources is
 // then the charges' source count, sources NULL).
 int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
-                       int32_t n_wavenumbers, int32_t n_charges, char* out, int64_t capacity, int64_t* length) {
+                       int32_t n_wavenumbers, int32_t n_charges, char* out, int64_t capacity, int64_t* length,
+                       const wost_model* models = nullptr, int32_t n_models = 0) {
     if (!pb || !length) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
+    if (n_models < 0 || n_models > WOST_MAX_SOURCES || (n_models > 0 && !models))
+        return fail(WOST_ERR_INVALID_ARG, "need 0..%d models", WOST_MAX_SOURCES);
     if (n_sources < 0 || n_sources > WOST_MAX_SOURCES || (n_charges == 0 && n_sources > 0 && !sources))
         return fail(WOST_ERR_INVALID_ARG, "need 0..%d sources", WOST_MAX_SOURCES);
     if (n_wavenumbers < 0 || n_wavenumbers * std::max(n_sources, 1) > WOST_MAX_SOURCES)
@@ -2052,7 +2177,16 @@ int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources,
         }
         ns = n_sources;
     }
-    build_program(h->fields, h->sigma_bar, h->prog);
+    if (n_models > 0) {   // wost_set_models' fields, without a device
+        h->n_sources = ns;
+        std::vector<HostField> conv;
+        if ((rc = convert_models(models, n_models, &conv)) != WOST_OK || (rc = check_models(h, n_models, conv)) != WOST_OK) {
+            delete h;
+            return rc;
+        }
+        install_models(h, n_models, conv);
+    }
+    build_program(h->fields, h->sigma_bar, h->prog, &h->model_fields);
     const WalkTraits t = walk_traits(h);
     // no device here: the segment angles of a compiled-in Neumann polyline come from the
     // host's atan2f (the kernels use the device's bits; this source is for offline study)
@@ -2101,6 +2235,52 @@ int wost_kernel_source_points(const wost_problem* pb, int32_t n_charges, int32_t
     return kernel_source_impl(pb, nullptr, n_sources, n_wavenumbers, n_charges, out, capacity, length);
 }
 
+int wost_kernel_source_models(const wost_problem* pb, const wost_model* models, int32_t n_models,
+                              const wost_field* const* sources, int32_t n_sources, int32_t n_wavenumbers, char* out,
+                              int64_t capacity, int64_t* length) {
+    return kernel_source_impl(pb, sources, n_sources, n_wavenumbers, 0, out, capacity, length, models, n_models);
+}
+
+int wost_set_models(wost_handle* h, const wost_model* models, int32_t n) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    if (n < 0 || (n > 0 && !models)) return fail(WOST_ERR_INVALID_ARG, "need n >= 0 models");
+    std::vector<HostField> conv;
+    if (n > 0) {
+        if (n > WOST_MAX_SOURCES) return fail(WOST_ERR_INVALID_ARG, "%d models exceed %d channels", n, WOST_MAX_SOURCES);
+        if (int rc = convert_models(models, n, &conv)) return rc;
+        if (int rc = check_models(h, n, conv)) return rc;
+    } else if (h->n_models == 0) {
+        return WOST_OK;
+    }
+    // (a refused set changes nothing: the handle's state is put back when the upload fails)
+    const int old_n = h->n_models;
+    const uint64_t old_sum = h->models_sum;
+    HostField old_pair[2] = {h->fields[SLOT_SIGMA], h->fields[SLOT_ALPHA]};
+    HostField old_own[2] = {h->own_fields[0], h->own_fields[1]};
+    std::vector<HostField> old_models = h->model_fields;
+    install_models(h, n, conv);
+    const hipError_t e = hipSetDevice(h->device);
+    int rc = e == hipSuccess ? upload_program(h) : fail(WOST_ERR_HIP, "hipSetDevice failed: %s", hipGetErrorString(e));
+    if (rc != WOST_OK) {
+        h->n_models = old_n;
+        h->models_sum = old_sum;
+        h->fields[SLOT_SIGMA] = std::move(old_pair[0]);
+        h->fields[SLOT_ALPHA] = std::move(old_pair[1]);
+        h->own_fields[0] = std::move(old_own[0]);
+        h->own_fields[1] = std::move(old_own[1]);
+        h->model_fields = std::move(old_models);
+        h->prog_dirty = true;   // (the next solve uploads the old program again)
+    }
+    return rc;
+}
+
+int wost_models_info(const wost_handle* h, int32_t* n, uint64_t* checksum) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    if (n) *n = h->n_models;
+    if (checksum) *checksum = h->n_models > 0 ? h->models_sum : 0;
+    return WOST_OK;
+}
+
 int wost_kernel_source_sources(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
                                char* out, int64_t capacity, int64_t* length) {
     return wost_kernel_source_channels(pb, sources, n_sources, 0, out, capacity, length);
@@ -2118,9 +2298,9 @@ int wost_set_wavenumbers(wost_handle* h, const double* k2, int32_t n) {
         return fail(WOST_ERR_UNSUPPORTED,
                     "wavenumbers need delta tracking (the screening k^2 alpha enters through the collision weight): "
                     "create the solver with sigma or alpha -- a constant alpha is enough");
-    if ((int64_t)n * h->n_sources > WOST_MAX_SOURCES)
-        return fail(WOST_ERR_INVALID_ARG, "%d wavenumbers x %d sources exceed %d channels", n, h->n_sources,
-                    WOST_MAX_SOURCES);
+    if ((int64_t)n * h->n_sources * std::max(h->n_models, 1) > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "%d wavenumbers x %d sources x %d models exceed %d channels", n, h->n_sources,
+                    std::max(h->n_models, 1), WOST_MAX_SOURCES);
     float v[WOST_MAX_SOURCES] = {};
     for (int j = 0; j < n; ++j) {
         if (!(k2[j] >= 0.0) || !std::isfinite(k2[j]) || !std::isfinite((float)k2[j]))

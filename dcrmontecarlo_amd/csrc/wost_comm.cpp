@@ -413,13 +413,18 @@ int wost_solve_distributed(wost_handle* h, wost_comm* c, const float* points, in
     RcclRun run{h, c, points, n_points, walks_per_point, max_steps, eps, seed};
     // wost_dist_solve_key's six values, then the checksum of the handle's point charges (0 when
     // it has none): ranks whose electrodes differ must not merge their sums
-    double key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // ... and of its models (wost_set_models; 0 when it has none)
+    double key[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (n_points >= 0 && (points || n_points == 0)) (void)wost_dist_solve_key(seed, eps, max_steps, points, n_points, key);
     uint64_t chk = 0;
     if (h) (void)wost_point_sources_info(h, nullptr, &chk);
     key[6] = (double)(uint32_t)chk;
     key[7] = (double)(uint32_t)(chk >> 32);
-    wost_dist_ops ops{&run, rccl_prepare, rccl_solve_range, rccl_allreduce, rccl_allgather, key, 8};
+    uint64_t mchk = 0;
+    if (h) (void)wost_models_info(h, nullptr, &mchk);
+    key[8] = (double)(uint32_t)mchk;
+    key[9] = (double)(uint32_t)(mchk >> 32);
+    wost_dist_ops ops{&run, rccl_prepare, rccl_solve_range, rccl_allreduce, rccl_allgather, key, 10};
     int64_t w0 = 0, w1 = 0;
     uint64_t steps = 0;
     const int rc = wost_distributed_run(&ops, c->n_ranks, c->rank, n_points, walks_per_point, row, point_stats, &w0,

@@ -751,7 +751,10 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
     if (opt.tree_qmargin >= 0) o << "#define WOST_TREE_QMARGIN " << opt.tree_qmargin << "\n";
     if (opt.tree_share_min >= 1) o << "#define WOST_TREE_SHARE_MIN " << opt.tree_share_min << "\n";
     if (opt.tree_batch >= 1) o << "#define WOST_TREE_BATCH " << (opt.tree_batch >= 4 ? 4 : opt.tree_batch >= 2 ? 2 : 1) << "\n";
-    o << "// generated by libwost (wost_jit.cpp): walk kernel, " << traits_name(t) << "\n"
+    const int nm = v.n_models >= 2 && prog.models != nullptr ? v.n_models : 1;   // NM (model batching)
+    o << "// generated by libwost (wost_jit.cpp): walk kernel, " << traits_name(t);
+    if (nm >= 2) o << ", " << nm << " models";
+    o << "\n"
       << "#include \"wost_walk.h\"\n\nnamespace {\nstruct GenFields {\n"
       << "    const float* grid;   // tabulated field values (WOST_FK_GRID) in the program buffer\n"
       << "    const char* pb;      // the program buffer (multi-source kernels read the sources' parameters)\n"
@@ -793,6 +796,38 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
                                     xf | (opt.vote_stats ? kVoteStatsFlag : 0)) : "        return wost::jet_const(1.0f);\n") << "    }\n";
     o << "    __device__ __forceinline__ bool detached() const { return "
       << ((fA.flags & WOST_FIELD_DETACHED) ? "true" : "false") << "; }\n";
+    if (nm >= 2) {
+        // model batching: models 1.. emitted exactly as sigma(), alpha() and alpha_jet() above
+        // (model 0), and the walk's calls that evaluate every model at one point
+        const int jx = xf | (opt.vote_stats ? kVoteStatsFlag : 0);
+        for (int m = 1; m < nm; ++m) {
+            const DField& mS = prog.models[2 * (m - 1)];
+            const DField& mA = prog.models[2 * (m - 1) + 1];
+            const std::string an = "alpha_m" + std::to_string(m);
+            o << "    __device__ __forceinline__ float sigma_m" << m << "(float x, float y) const {\n"
+              << (mS.present ? value_body(mS, terms, factors) : "        return 0.0f;\n") << "    }\n";
+            o << "    __device__ __forceinline__ float " << an << "(float x, float y) const {\n"
+              << (mA.present ? value_body(mA, terms, factors) : "        return 1.0f;\n") << "    }\n";
+            o << "    __device__ __forceinline__ wost::Jet alpha_jet_m" << m << "(float x, float y) const {\n"
+              << (mA.present ? jet_body(mA, terms, factors, (mA.flags & WOST_FIELD_DETACHED) ? nullptr : an.c_str(), jx)
+                             : "        return wost::jet_const(1.0f);\n")
+              << "    }\n";
+        }
+        o << "    __device__ __forceinline__ void sigma_multi(float x, float y, float* out) const {\n"
+          << "        out[0] = sigma(x, y);\n";
+        for (int m = 1; m < nm; ++m) o << "        out[" << m << "] = sigma_m" << m << "(x, y);\n";
+        o << "    }\n    __device__ __forceinline__ void alpha_multi(float x, float y, float* out) const {\n"
+          << "        out[0] = alpha(x, y);\n";
+        for (int m = 1; m < nm; ++m) o << "        out[" << m << "] = alpha_m" << m << "(x, y);\n";
+        o << "    }\n    __device__ __forceinline__ void alpha_jet_multi(float x, float y, wost::Jet* out) const {\n"
+          << "        out[0] = alpha_jet(x, y);\n";
+        for (int m = 1; m < nm; ++m) o << "        out[" << m << "] = alpha_jet_m" << m << "(x, y);\n";
+        o << "    }\n    __device__ __forceinline__ bool detached_multi(int m) const {\n"
+          << "        const bool d[" << nm << "] = {" << ((fA.flags & WOST_FIELD_DETACHED) ? "true" : "false");
+        for (int m = 1; m < nm; ++m)
+            o << ", " << ((prog.models[2 * (m - 1) + 1].flags & WOST_FIELD_DETACHED) ? "true" : "false");
+        o << "};\n        return d[m];\n    }\n";
+    }
     o << "    __device__ __forceinline__ float sigma_bar() const { return " << lit(hdr.sigma_bar) << "; }\n";
     o << "    __device__ __forceinline__ float sqrt_sigma_bar() const { return " << lit(hdr.sqrt_sigma_bar) << "; }\n";
     o << "    __device__ __forceinline__ float inv_sigma_bar() const { return " << lit(hdr.inv_sigma_bar) << "; }\n";
@@ -910,15 +945,18 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
       << ", " << v.n_sources << ", " << (t.fix ? "true" : "false") << ", "
       << (v.global_polylines ? "true" : "false");
     // NK (a handle without wavenumbers: its kernel as ever), then PC (likewise without point charges)
-    if (v.n_wavenumbers >= 1 || v.n_charges >= 1) o << ", " << std::max(v.n_wavenumbers, 1);
-    if (v.n_charges >= 1) o << ", " << v.n_charges;
+    // ... then NM (likewise without models)
+    if (v.n_wavenumbers >= 1 || v.n_charges >= 1 || nm >= 2) o << ", " << std::max(v.n_wavenumbers, 1);
+    if (v.n_charges >= 1 || nm >= 2) o << ", " << v.n_charges;
+    if (nm >= 2) o << ", " << nm;
     o << ">(A, fld, smem);\n}\n";
     if (delta)   // alpha at the query points, with these fields (WalkArgs::point_alpha)
         o << "extern \"C\" __global__ void __launch_bounds__(256)\n"
           << "wost_point_alpha_jit(const char* prog, const float2* pts, long long n, float* out) {\n"
           << "    const GenFields fld{reinterpret_cast<const float*>(prog + "
           << program_grid_offset(hdr.n_terms_total, hdr.n_factors_total) << "ull), prog};\n"
-          << "    wost::point_alpha_body(pts, (int64_t)n, out, fld);\n}\n";
+          << (nm >= 2 ? "    wost::point_alpha_multi_body<" + std::to_string(nm) + ">(pts, (int64_t)n, out, fld);\n}\n"
+                      : std::string("    wost::point_alpha_body(pts, (int64_t)n, out, fld);\n}\n"));
     return o.str();
 }
 

@@ -31,10 +31,16 @@ bool jit_const_neumann(const Options& o, const WalkTraits& t, int nn);
 bool jit_fused_neumann_scan(const Options& o, const WalkTraits& t, int nn);
 
 // The fields a kernel compiles in: the program's header, terms and factors.
+// models: the (sigma, alpha) field pairs of models 1.. of a model-batched kernel (variant
+// n_models >= 2; model 0 is the header's SLOT_SIGMA / SLOT_ALPHA): 2 * (n_models - 1)
+// descriptors into the same terms and factors, in slots after the extra sources. Only
+// generated code reads them, so they stay on the host: the header the device reads is
+// unchanged. Null otherwise.
 struct ProgramView {
     const DProgram* hdr;
     const DTerm* terms;
     const DFactor* factors;
+    const DField* models = nullptr;
 };
 // The polylines (Dirichlet dverts[2*nd], Neumann nverts[2*nn]; short ones are compiled in)
 // and seg_phi: the device's per-segment normal angles of a compiled-in Neumann polyline

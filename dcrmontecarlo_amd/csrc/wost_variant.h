@@ -40,6 +40,8 @@ struct KernelVariant {
     int n_sources = 1;               // NS: sources a walk scores (SLOT_F, SLOT_EXTRA..)
     int n_wavenumbers = 0;           // NK: attenuations a walk carries; 0: none set (no k2 read)
     int n_charges = 0;               // PC: point charges a walk scores (the count only: they are run-time data)
+    int n_models = 0;                // NM: (sigma, alpha) models a walk scores (wost_set_models); 0: none set, 1: one
+                                     // set (the program carries its fields: the kernel of a handle made with them)
     int block = 256;                 // threads per workgroup the kernel is launched with
     bool global_polylines = false;   // polylines not compiled in are read from global memory (wost_walk.h GL)
     int tree_stage = 0;              // tree kernels: 0 = the tree through L1/L2, 1 = its records in LDS
@@ -49,7 +51,8 @@ struct KernelVariant {
 
 inline bool operator==(const KernelVariant& a, const KernelVariant& b) {
     return a.traits == b.traits && a.record == b.record && a.n_sources == b.n_sources &&
-           a.n_wavenumbers == b.n_wavenumbers && a.n_charges == b.n_charges && a.block == b.block &&
+           a.n_wavenumbers == b.n_wavenumbers && a.n_charges == b.n_charges && a.n_models == b.n_models &&
+           a.block == b.block &&
            a.global_polylines == b.global_polylines && a.tree_stage == b.tree_stage && a.exact_trig == b.exact_trig;
 }
 

@@ -245,6 +245,17 @@ __device__ __forceinline__ void point_alpha_body(const float2* pts, int64_t n, f
         out[i] = fld.alpha(q.x, q.y);
     }
 }
+// ... of every model of a model-batched kernel (NM > 1): out[m * n + i] = alpha_m(pts[i])
+template <int NM, class F>
+__device__ __forceinline__ void point_alpha_multi_body(const float2* pts, int64_t n, float* out, const F& fld) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float2 q = pts[i];
+        float a[NM];
+        fld.alpha_multi(q.x, q.y, a);
+#pragma unroll
+        for (int m = 0; m < NM; ++m) out[(int64_t)m * n + i] = a[m];
+    }
+}
 
 constexpr int kWalkBlock = 256;
 // workgroup of the field-specialised tree kernels that stage the tree's records in LDS:
@@ -842,6 +853,16 @@ __device__ __forceinline__ Hit intersect_polylines_tree_wave(const SegTree& t, f
 // precompiled ones, NK = 1, and the specialised ones of a handle with wavenumbers set); the
 // others compile the add out, so a handle without wavenumbers runs the kernel it always ran.
 // NK > 1 tree kernels run without walk pools (a parked walk holds one w).
+// NM > 1 (shared-path model batching): the same argument for the whole (sigma,
+// alpha) pair. The step, the collision test, the sampler and the Green's norm read sigma_bar
+// and the geometry only; the conductivity enters through alpha_jet(y) and sigma(y) (the
+// collision weight), alpha(next) / alpha(x) (the factor sqrt(a_new / alpha(x))), the source
+// score's rsq(alpha(y) alpha(x)) and alpha(x0). One walk carries NW = NM * NK weights
+// w[m * NK + j] and ax[NM], and scores NM * NK * NS channels, c = (m * NK + j) * NS + s (model
+// major): each bit for bit the single solve of model m on this sigma_bar. The Fields policy
+// then provides alpha_multi(x, y, float[NM]), alpha_jet_multi(x, y, Jet[NM]), sigma_multi(x,
+// y, float[NM]) and detached_multi(m); A.point_alpha is [NM][n_points]. Field-specialised
+// kernels only, no walk pools, no point charges.
 // PC > 0 (point sources, FIX only): the handle's source is PC point charges
 // q_p delta(z_p), charge p belonging to source channel s(p) (A.charges, run-time data). A
 // step scores each charge inside its ball and visible from x with q_p G_B(x, z_p)
@@ -908,7 +929,7 @@ __device__ __forceinline__ void pool_unlock(uint32_t* pool, int lane, uint32_t n
 // walks are the same walks and the dynamic VALU counter grows by that phase's cost plus
 // the merge's ~3 instructions. 1 Dirichlet distance, 2 Philox draw, 4 direction cos/sin,
 // 8 Neumann ray query (scan kernels), 16 radial sampler, 32 screened G_norm, 64 alpha jet
-// at the sample, 128 alpha at the ray's point, 256 the source f, 512 sigma'.
+// at the sample (NM > 1: model 0's), 128 alpha at the ray's point, 256 the source f, 512 sigma'.
 #ifndef WOST_ABL_DUP
 #define WOST_ABL_DUP 0
 #endif
@@ -961,7 +982,7 @@ __device__ __forceinline__ void walk_sincos(float theta, float& sn, float& cs, b
 #define WOST_PIN_U4(u) ((void)0)
 #endif
 template <bool NEU, bool SRC, bool DELTA, bool TREE, bool REC, int NS = 1, bool FIX = false, bool GL = false,
-          int NK = 1, int PC = 0, class F>
+          int NK = 1, int PC = 0, int NM = 1, class F>
 __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsigned char* smem) {
     // the walk's position updates round op by op like the reference (torch CPU
     // has no FMA contraction); the field math it calls keeps its own setting
@@ -969,9 +990,12 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     static_assert(NS >= 1 && (NS == 1 || SRC) && (NS == 1 || !REC), "multi-source walks need a source, no recorder");
     static_assert(NK >= 1 && (NK == 1 || (DELTA && !REC && WOST_WAVENUMBERS)) && NK * NS <= WOST_MAX_SOURCES,
                   "wavenumber channels need delta tracking, no recorder, at most WOST_MAX_SOURCES channels");
+    static_assert(NM >= 1 && (NM == 1 || (DELTA && !REC && PC == 0)) && NM * NK * NS <= WOST_MAX_SOURCES,
+                  "model channels need delta tracking, no recorder, no point charges, at most WOST_MAX_SOURCES channels");
     static_assert(PC >= 0 && PC <= WOST_MAX_POINT_CHARGES && (PC == 0 || (FIX && SRC && !REC)),
                   "point sources need compat=\"fixed\", a source mode, no recorder, at most WOST_MAX_POINT_CHARGES charges");
-    constexpr int NC = NK * NS;   // channels: c = j * NS + s
+    constexpr int NW = NM * NK;   // weights: wc = m * NK + j
+    constexpr int NC = NW * NS;   // channels: c = (m * NK + j) * NS + s
     constexpr bool kStageD = !F::kConstDirichlet && !GL;
     // the Neumann polyline is staged also when compiled in (FIX scans sN itself; a few
     // hundred bytes otherwise)
@@ -1021,7 +1045,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         for (int i = threadIdx.x; i < kGnormCells; i += blockDim.x) sG[i] = g[i];
     }
     // this workgroup's walk pools (header: lock, walks parked near, walks parked far)
-    uint32_t* const pool = (TREE && WOST_TREE_POOL && NK == 1 && PC == 0 && A.pool != nullptr)
+    uint32_t* const pool = (TREE && WOST_TREE_POOL && NK == 1 && PC == 0 && NM == 1 && A.pool != nullptr)
                                ? A.pool + (size_t)blockIdx.x * (size_t)A.pool_wg_words : nullptr;
     if (pool != nullptr && threadIdx.x < 4) pool[threadIdx.x] = 0u;
     __syncthreads();
@@ -1073,10 +1097,12 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     bool onB = false;           // onBoundary
     float phi = 0.f;            // atan2 of currentNormal (:228), set when onB
     int xcode = 0;              // (PC > 0) boundary_code of the current point: its segment and inward side
-    float w[NK];                // attenuation_coef (one per wavenumber)
+    float ax[NM];               // alpha(current_point), cached (one per model)
 #pragma unroll
-    for (int j = 0; j < NK; ++j) w[j] = 1.f;
-    float ax = 1.f;             // alpha(current_point), cached
+    for (int m = 0; m < NM; ++m) ax[m] = 1.f;
+    float w[NW];                // attenuation_coef (one per model and wavenumber)
+#pragma unroll
+    for (int j = 0; j < NW; ++j) w[j] = 1.f;
     U4 rn_ahead{0u, 0u, 0u, 0u};   // (WOST_PHILOX_AHEAD) the words of this walk's step k
     float total[NC];            // this walk's contributions (one per channel)
 #pragma unroll
@@ -1106,7 +1132,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             float g = g0;
             if (DELTA) g = g0 * w[0];
 #pragma unroll
-            for (int j = 0; j < NK; ++j) {
+            for (int j = 0; j < NW; ++j) {
                 const float gj = (DELTA && j > 0) ? g0 * w[j] : g;
 #pragma unroll
                 for (int s = 0; s < NS; ++s) total[j * NS + s] = total[j * NS + s] + gj;
@@ -1159,7 +1185,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     r[6 * P] = __builtin_bit_cast(uint32_t, dD);
                     r[7 * P] = (uint32_t)k | (onB ? 0x80000000u : 0u);
                     r[8 * P] = __builtin_bit_cast(uint32_t, phi); r[9 * P] = __builtin_bit_cast(uint32_t, w[0]);
-                    r[10 * P] = __builtin_bit_cast(uint32_t, ax);
+                    r[10 * P] = __builtin_bit_cast(uint32_t, ax[0]);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) r[(11 + s) * P] = __builtin_bit_cast(uint32_t, total[s]);
                     active = false;
@@ -1179,7 +1205,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     const uint32_t kb = r[7 * P];
                     k = (int)(kb & 0x7fffffffu); onB = (kb >> 31) != 0u;
                     phi = __builtin_bit_cast(float, r[8 * P]); w[0] = __builtin_bit_cast(float, r[9 * P]);
-                    ax = __builtin_bit_cast(float, r[10 * P]);
+                    ax[0] = __builtin_bit_cast(float, r[10 * P]);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) total[s] = __builtin_bit_cast(float, r[(11 + s) * P]);
                     pw = philox_walk(wid, A.key0, A.key1);
@@ -1254,10 +1280,14 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     }
                 }
 #pragma unroll
-                for (int j = 0; j < NK; ++j) w[j] = 1.f;
+                for (int j = 0; j < NW; ++j) w[j] = 1.f;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) total[c] = 0.f;
-                if (DELTA) ax = A.point_alpha[pid];                // alpha(x0), precomputed per point
+                if (DELTA) ax[0] = A.point_alpha[pid];             // alpha(x0), precomputed per point
+                if constexpr (NM > 1) {                            // ... and per model: [NM][n_points]
+#pragma unroll
+                    for (int m = 1; m < NM; ++m) ax[m] = A.point_alpha[(size_t)m * (size_t)A.n_points + pid];
+                }
                 active = true;
             }
             c_next += take;
@@ -1290,7 +1320,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     const uint32_t kb = r[7 * P];
                     k = (int)(kb & 0x7fffffffu); onB = (kb >> 31) != 0u;
                     phi = __builtin_bit_cast(float, r[8 * P]); w[0] = __builtin_bit_cast(float, r[9 * P]);
-                    ax = __builtin_bit_cast(float, r[10 * P]);
+                    ax[0] = __builtin_bit_cast(float, r[10 * P]);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) total[s] = __builtin_bit_cast(float, r[(11 + s) * P]);
                     pw = philox_walk(wid, A.key0, A.key1);
@@ -1461,6 +1491,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         bool clipped = false;
         float gnorm = 0.f;
         Jet aj{0.f, 0.f, 0.f, 0.f};
+        Jet ajm[NM];                                                 // (NM > 1) every model's jet at y; ajm[0] = aj
         WOST_PHASE("sample_and_clip");
         if (SRC) {                                                   // :242-258
             float rs;
@@ -1507,13 +1538,19 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 gnorm = greens_norm_from_table(sG, r * sqrt_sb, r, inv_sb);   // solvers/utils.py:29-44
                 if (WOST_ABL_DUP & 32) gnorm = dup_merge(gnorm, greens_norm_from_table(sG, dup_opq(r) * sqrt_sb, r, inv_sb));
                 WOST_PHASE("alpha_jet");
-                aj = fld.alpha_jet(yx, yy);
+                if constexpr (NM > 1) {
+                    fld.alpha_jet_multi(yx, yy, ajm);
+                    aj = ajm[0];
+                } else {
+                    aj = fld.alpha_jet(yx, yy);
+                }
                 if (WOST_ABL_DUP & 64) {
                     const Jet a2 = fld.alpha_jet(dup_opq(yx), yy);
                     aj.v = dup_merge(aj.v, a2.v);
                     aj.gx = dup_merge(aj.gx, a2.gx);
                     aj.gy = dup_merge(aj.gy, a2.gy);
                     aj.lap = dup_merge(aj.lap, a2.lap);
+                    if constexpr (NM > 1) ajm[0] = aj;   // (the score and sigma' read model 0's jet from ajm)
                 }
             }
             WOST_PHASE("source_contribution");
@@ -1560,7 +1597,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                                 float v;
                                 if constexpr (DELTA)
                                     v = (q * ball_greens_screened(rp, r, sqrt_sb)) *
-                                        f_rsq(charge_float(A.charges, CHG_ALPHA + p) * ax);
+                                        f_rsq(charge_float(A.charges, CHG_ALPHA + p) * ax[0]);
                                 else
                                     v = q * ball_greens(rp, r);
                                 const int sp = charge_int(A.charges, CHG_SOURCE + p);
@@ -1583,7 +1620,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     float f = fld.f(yx, yy);
                     if (WOST_ABL_DUP & 256) f = dup_merge(f, fld.f(dup_opq(yx), yy));
                     if (DELTA)
-                        c = (f * gnorm) * f_rsq(aj.v * ax) * w[0];  // :253-254
+                        c = (f * gnorm) * f_rsq(aj.v * ax[0]) * w[0];  // :253-254
                     else
                         c = f * ((r * r) / 4.0f);                        // :256, utils.py:61
                 }
@@ -1593,15 +1630,18 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 float fv[NS];
                 if constexpr (NS == 1) fv[0] = fld.f(yx, yy);
                 else fld.f_multi(yx, yy, fv);
-                const float sa = DELTA ? f_rsq(aj.v * ax) : 0.0f;
                 const float q = DELTA ? 0.0f : ((r * r) / 4.0f);
 #pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const float fg = DELTA ? ((fv[s] * gnorm) * sa) : fv[s] * q;
+                for (int m = 0; m < NM; ++m) {
+                    const float sa = DELTA ? f_rsq((NM > 1 ? ajm[m].v : aj.v) * ax[m]) : 0.0f;
 #pragma unroll
-                    for (int j = 0; j < NK; ++j) {
-                        const float c = DELTA ? fg * w[j] : fg;
-                        total[j * NS + s] = total[j * NS + s] + c;
+                    for (int s = 0; s < NS; ++s) {
+                        const float fg = DELTA ? ((fv[s] * gnorm) * sa) : fv[s] * q;
+#pragma unroll
+                        for (int j = 0; j < NK; ++j) {
+                            const float c = DELTA ? fg * w[m * NK + j] : fg;
+                            total[(m * NK + j) * NS + s] = total[(m * NK + j) * NS + s] + c;
+                        }
                     }
                 }
             } else {
@@ -1623,71 +1663,116 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             const float mu = u01(rn.z);
             // collision: mu <= sigma_bar |G| and the sample before the ray's boundary point
             const bool collide = !(mu > sigma_bar * gnorm) && !clipped;
-            float anew = aj.v;                                       // a collision, or a clipped sample (y = z)
-            if (!collide && !clipped) anew = fld.alpha(xnx, xny);
-            float sc[NK];
+            float anew[NM];                                          // a collision, or a clipped sample (y = z)
+            anew[0] = aj.v;
+            if constexpr (NM > 1) {
 #pragma unroll
-            for (int j = 0; j < NK; ++j) sc[j] = 1.0f;
+                for (int m = 1; m < NM; ++m) anew[m] = ajm[m].v;
+            }
+            if (!collide && !clipped) {
+                if constexpr (NM > 1) fld.alpha_multi(xnx, xny, anew);
+                else anew[0] = fld.alpha(xnx, xny);
+            }
+            float sc[NW];
+#pragma unroll
+            for (int j = 0; j < NW; ++j) sc[j] = 1.0f;
             if (collide) {
-                const float spv = sigma_prime_from(aj, fld.sigma(yx, yy), fld.detached());
+                float spv[NM];
+                if constexpr (NM > 1) {
+                    float sg[NM];
+                    fld.sigma_multi(yx, yy, sg);
 #pragma unroll
-                for (int j = 0; j < NK; ++j) {
-                    if constexpr (WOST_WAVENUMBERS) sc[j] = 1.0f - (spv + A.k2[j]) * inv_sb;   // kept signed
-                    else sc[j] = 1.0f - spv * inv_sb;
+                    for (int m = 0; m < NM; ++m) spv[m] = sigma_prime_from(ajm[m], sg[m], fld.detached_multi(m));
+                } else {
+                    spv[0] = sigma_prime_from(aj, fld.sigma(yx, yy), fld.detached());
+                }
+#pragma unroll
+                for (int m = 0; m < NM; ++m) {
+#pragma unroll
+                    for (int j = 0; j < NK; ++j) {
+                        if constexpr (WOST_WAVENUMBERS) sc[m * NK + j] = 1.0f - (spv[m] + A.k2[j]) * inv_sb;   // kept signed
+                        else sc[m * NK + j] = 1.0f - spv[m] * inv_sb;
+                    }
                 }
             }
-            const float wr = f_sqrt(f_div(anew, ax));                // shared by the wavenumbers
 #pragma unroll
-            for (int j = 0; j < NK; ++j) {
-                const float wt = w[j] * wr;
-                w[j] = collide ? wt * sc[j] : wt;
+            for (int m = 0; m < NM; ++m) {
+                const float wr = f_sqrt(f_div(anew[m], ax[m]));      // shared by the wavenumbers
+#pragma unroll
+                for (int j = 0; j < NK; ++j) {
+                    const float wt = w[m * NK + j] * wr;
+                    w[m * NK + j] = collide ? wt * sc[m * NK + j] : wt;
+                }
+                ax[m] = anew[m];
             }
             px = collide ? yx : xnx;
             py = collide ? yy : xny;
             onB = collide ? false : onB;                             // a collision point is interior
             if constexpr (PC > 0) xcode = collide ? 0 : xcode;
-            ax = anew;
         } else if (DELTA) {                                          // :271-284
             const float mu = u01(rn.z);
             const bool accept = mu > sigma_bar * gnorm;              // :273-275
             // the two branches share the weight update w * sqrt(a_new / alpha(x));
             // only the field evaluations stay divergent
-            float anew = aj.v;                                       // collision, or a clipped accept
+            float anew[NM];                                          // collision, or a clipped accept
+            anew[0] = aj.v;
+            if constexpr (NM > 1) {
+#pragma unroll
+                for (int m = 1; m < NM; ++m) anew[m] = ajm[m].v;
+            }
 #if !defined(WOST_ABL_NO_ALPHA_Z)
             if (accept && !clipped) {
-                anew = fld.alpha(xnx, xny);                          // :277
-                if (WOST_ABL_DUP & 128) anew = dup_merge(anew, fld.alpha(dup_opq(xnx), xny));
+                if constexpr (NM > 1) {
+                    fld.alpha_multi(xnx, xny, anew);
+                } else {
+                    anew[0] = fld.alpha(xnx, xny);                   // :277
+                    if (WOST_ABL_DUP & 128) anew[0] = dup_merge(anew[0], fld.alpha(dup_opq(xnx), xny));
+                }
             }
 #endif
-            float sc[NK];
+            float sc[NW];
 #pragma unroll
-            for (int j = 0; j < NK; ++j) sc[j] = 1.0f;
+            for (int j = 0; j < NW; ++j) sc[j] = 1.0f;
 #if defined(WOST_ABL_NO_SIGMA_PRIME)
             if (false) {
 #else
             if (!accept) {
 #endif
-                float spv = sigma_prime_from(aj, fld.sigma(yx, yy), fld.detached());  // :281
-                if (WOST_ABL_DUP & 512)
-                    spv = dup_merge(spv, sigma_prime_from(Jet{dup_opq(aj.v), aj.gx, aj.gy, aj.lap},
-                                                          fld.sigma(dup_opq(yx), yy), fld.detached()));
+                float spv[NM];
+                if constexpr (NM > 1) {
+                    float sg[NM];
+                    fld.sigma_multi(yx, yy, sg);
 #pragma unroll
-                for (int j = 0; j < NK; ++j) {
-                    float scj;
-                    if constexpr (WOST_WAVENUMBERS) scj = 1.0f - (spv + A.k2[j]) * inv_sb;
-                    else scj = 1.0f - spv * inv_sb;
-                    sc[j] = (0.0f > scj) ? 0.0f : scj;               // Python max(., 0.0) (:282)
+                    for (int m = 0; m < NM; ++m) spv[m] = sigma_prime_from(ajm[m], sg[m], fld.detached_multi(m));
+                } else {
+                    spv[0] = sigma_prime_from(aj, fld.sigma(yx, yy), fld.detached());  // :281
+                    if (WOST_ABL_DUP & 512)
+                        spv[0] = dup_merge(spv[0], sigma_prime_from(Jet{dup_opq(aj.v), aj.gx, aj.gy, aj.lap},
+                                                                    fld.sigma(dup_opq(yx), yy), fld.detached()));
+                }
+#pragma unroll
+                for (int m = 0; m < NM; ++m) {
+#pragma unroll
+                    for (int j = 0; j < NK; ++j) {
+                        float scj;
+                        if constexpr (WOST_WAVENUMBERS) scj = 1.0f - (spv[m] + A.k2[j]) * inv_sb;
+                        else scj = 1.0f - spv[m] * inv_sb;
+                        sc[m * NK + j] = (0.0f > scj) ? 0.0f : scj;  // Python max(., 0.0) (:282)
+                    }
                 }
             }
-            const float wr = f_sqrt(f_div(anew, ax));               // :277 / :283, shared by the wavenumbers
 #pragma unroll
-            for (int j = 0; j < NK; ++j) {
-                const float wt = w[j] * wr;
-                w[j] = accept ? wt : wt * sc[j];
+            for (int m = 0; m < NM; ++m) {
+                const float wr = f_sqrt(f_div(anew[m], ax[m]));      // :277 / :283, shared by the wavenumbers
+#pragma unroll
+                for (int j = 0; j < NK; ++j) {
+                    const float wt = w[m * NK + j] * wr;
+                    w[m * NK + j] = accept ? wt : wt * sc[m * NK + j];
+                }
+                ax[m] = anew[m];
             }
             px = accept ? xnx : yx;
             py = accept ? xny : yy;
-            ax = anew;
         } else {
             px = xnx; py = xny;                                      // :287
         }

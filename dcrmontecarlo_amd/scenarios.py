@@ -136,10 +136,13 @@ def variable_coefficients(n_points: int = 256, n_walks: int = 100_000) -> Scenar
                     reference="tests/testWostVariableCoefficients.py:185-264")
 
 
-def dcr_alpha_geophysical() -> F.Field:
-    """conductivity_field, tests/testGeophysicalScenario.py:35-55."""
+def dcr_alpha_geophysical(conductive_scale: float = 1.0) -> F.Field:
+    """conductivity_field, tests/testGeophysicalScenario.py:35-55. conductive_scale scales the
+    conductive inclusion's conductivity (1: the reference's field): the perturbed models of
+    paired differences and sensitivities (WostSolver_2D.solve_models)."""
     bg = 1e2
-    return bg + (1e1 - bg) * F.smooth_circle((-20.0, -30.0), 10.0) + (1e3 - bg) * F.smooth_circle((25.0, -40.0), 10.0)
+    return (bg + (1e1 - bg) * F.smooth_circle((-20.0, -30.0), 10.0)
+            + (1e3 * conductive_scale - bg) * F.smooth_circle((25.0, -40.0), 10.0))
 
 
 def dcr_source_geophysical() -> F.Field:

@@ -109,11 +109,13 @@ def _problem(dxy, nxy, g, f, sigma, alpha, compat, device, sigma_bar):
 
 def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoundary=None, source=None,
                   sigma=None, alpha=None, *, sigma_bar: float | None = None, compat: str = "reference",
-                  sources=None, n_wavenumbers: int = 0) -> str:
+                  sources=None, n_wavenumbers: int = 0, models=None) -> str:
     """HIP source of the field-specialised walk kernel a WostSolver_2D with these
     arguments would compile (no device needed; wost_kernel_source). sources: the fields
     of a multi-source solve (solve_sources; wost_kernel_source_sources); n_wavenumbers: the
-    wavenumbers of set_wavenumbers (wost_kernel_source_channels; 0: none)."""
+    wavenumbers of set_wavenumbers (wost_kernel_source_channels; 0: none); models: the
+    (sigma, alpha) pairs of set_models (wost_kernel_source_models; None: that entry point is
+    not used, an empty list: it is, with no model)."""
     dxy = np.asarray(_np(dirichletBoundary.points), dtype=np.float32).reshape(-1, 2)
     nxy = None if neumannBoundary is None else np.asarray(_np(neumannBoundary.points), dtype=np.float32).reshape(-1, 2)
     conv = _Converter(_bounds_of(dxy, nxy))
@@ -131,6 +133,19 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
     n = ctypes.c_int64(0)
     call = lambda buf, cap: _lib.lib.wost_kernel_source_channels(ctypes.byref(prob), arr, len(packed),
                                                                   int(n_wavenumbers), buf, cap, ctypes.byref(n))
+    if models is not None:
+        marr = (_lib.WostModel * max(1, len(models)))()
+        for m, (sg, al) in enumerate(models):
+            ms, ma = conv(sg, f"models[{m}].sigma"), conv(al, f"models[{m}].alpha", is_alpha=True)
+            if ma is not None and ma.is_constant():
+                ma = detach(ma)
+            for name, fld in (("sigma", ms), ("alpha", ma)):
+                wf, k = _lib.make_field(fld)
+                keep.append(k)
+                setattr(marr[m], name, ctypes.pointer(wf) if wf is not None else None)
+        call = lambda buf, cap: _lib.lib.wost_kernel_source_models(ctypes.byref(prob), marr, len(models), arr,
+                                                                    len(packed), int(n_wavenumbers), buf, cap,
+                                                                    ctypes.byref(n))
     _lib.check(call(None, 0), "wost_kernel_source")
     buf = ctypes.create_string_buffer(n.value + 1)
     _lib.check(call(buf, n.value + 1), "wost_kernel_source")
@@ -270,6 +285,7 @@ class WostSolver_2D:
         self.last_point_sums = None   # (sum, sum^2, steps) per point of the last solve
         self.wavenumbers = None       # set_wavenumbers: the k of the handle's channels, or None
         self.point_sources = None     # set_point_sources: the sources' charge lists, or None
+        self.models = None            # set_models: the models' (sigma, alpha) fields, or None
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -522,10 +538,11 @@ class WostSolver_2D:
         for c0 in range(0, len(fields), _lib.WOST_MAX_SOURCES):
             with self.sources_installed(fields[c0:c0 + _lib.WOST_MAX_SOURCES]) as S:
                 if self.num_channels() != S:   # (wost_solve_multi would write rows of 2C+1, values [walks][C])
-                    raise ValueError(f"solve_sources scores one value per source, but the solver has "
-                                     f"{self.num_channels() // S} wavenumbers set (set_wavenumbers): use "
-                                     "solve_wavenumbers(points, k, sources=...), or clear them with "
-                                     "set_wavenumbers(None)")
+                    raise ValueError(f"solve_sources scores one value per source, but the solver scores "
+                                     f"{self.num_channels() // S} channels per source: wavenumbers "
+                                     "(set_wavenumbers) or models (set_models) are set. Use "
+                                     "solve_wavenumbers(points, k, sources=...) or solve_models(points, models, "
+                                     "sources=...), or clear them with set_wavenumbers(None) / set_models(None)")
                 s = np.zeros((n, 2 * S + 1), np.float64)
                 wv = np.empty(n * nWalks * S, np.float32) if want_walks else None
                 ws = np.empty(n * nWalks, np.uint32) if want_walks else None
@@ -628,7 +645,8 @@ class WostSolver_2D:
             with self.point_sources_installed(chunk) as S:
                 if self.num_channels() != S:
                     raise ValueError("solve_point_sources scores one value per source, but the solver has wavenumbers "
-                                     "set: use solve_wavenumbers(points, k, sources=...)")
+                                     "or models set: use solve_wavenumbers(points, k, sources=...), or clear them "
+                                     "with set_wavenumbers(None) / set_models(None)")
                 s = np.zeros((n, 2 * S + 1), np.float64)
                 wv = np.empty(n * nWalks * S, np.float32) if want_walks else None
                 ws = np.empty(n * nWalks, np.uint32) if want_walks else None
@@ -697,6 +715,10 @@ class WostSolver_2D:
         kk = np.atleast_1d(np.asarray(k, np.float64)).ravel()
         if kk.size < 1:
             raise ValueError("k must hold at least one wavenumber")
+        if self.num_models:   # (wost_solve_multi would write rows of 2C+1 with the models' channels)
+            raise ValueError(f"solve_wavenumbers scores one value per wavenumber and source, but the solver has "
+                             f"{self.num_models} models set (set_models): use solve_models(points, models, k=..., "
+                             "sources=...), or clear them with set_models(None)")
         points = sources is not None and len(sources) > 0 and all(is_point_source(s) or isinstance(s, (list, tuple))
                                                                  for s in sources)
         if sources is not None and not points and any(is_point_source(s) for s in sources):
@@ -732,6 +754,8 @@ class WostSolver_2D:
                             k1 = min(K, k0 + k_chunk)
                             self.set_wavenumbers(kk[k0:k1])
                             C = (k1 - k0) * (s1 - s0)
+                            if self.num_channels() != C:   # (the buffers below hold C values per walk)
+                                raise RuntimeError(f"the handle scores {self.num_channels()} channels, expected {C}")
                             rows = np.zeros((n, 2 * C + 1), np.float64)
                             wv = np.empty(n * nWalks * C, np.float32) if want_walks else None
                             ws = np.empty(n * nWalks, np.uint32) if want_walks else None
@@ -787,6 +811,195 @@ class WostSolver_2D:
         channels: the paths do not depend on them)."""
         _, vals, steps = self._solve_channels(solvePoints, k, sources, nWalks, maxSteps, eps, seed, True)
         return (vals[:, 0] if sources is None else vals), steps
+
+    # ---- shared-path model batching (DESIGN.md 7c, include/wost.h wost_set_models) ----------
+    def model_fields(self, models) -> list:
+        """The device fields of a list of models, each a ``(sigma, alpha)`` pair of fields,
+        numbers or callables (``None``: sigma = 0 / alpha = 1, as the constructor's): a list
+        of ``(sigma_field | None, alpha_field | None)``; a constant alpha is detached (Q9)."""
+        out = []
+        for m, pair in enumerate(models):
+            try:
+                sg, al = pair
+            except (TypeError, ValueError):
+                raise TypeError(f"models[{m}] must be a (sigma, alpha) pair") from None
+            if sg is None and al is None:
+                raise ValueError(f"models[{m}] has neither sigma nor alpha")
+            s = self._conv(sg, f"models[{m}].sigma")
+            a = self._conv(al, f"models[{m}].alpha", is_alpha=True)
+            if a is not None and a.is_constant():
+                a = detach(a)
+            out.append((s, a))
+        return out
+
+    def set_models(self, models=None):
+        """Score the conductivity models ``models`` -- ``(sigma, alpha)`` pairs -- with every
+        walk, or (``None`` or empty) the solver's own fields again. Under delta tracking a
+        walk's path depends only on ``sigma_bar`` and the geometry, so one set of walks
+        scores them all: channel ``(m, j, s)`` of model m, wavenumber j, source s is bit for
+        bit the single solve of a solver created with model m's fields and this solver's
+        ``sigma_bar``. ``sigma_bar`` stays the one fixed at construction: choose it >= the
+        largest sigma' of any model (``survey.sigma_bar_for_models``). At most
+        WOST_MAX_SOURCES channels (models x wavenumbers x sources) per launch;
+        ``solve_models`` chunks larger requests. Needs delta tracking; several models cannot
+        be combined with point sources."""
+        fields = self.model_fields(models) if models is not None and len(models) else []
+        if not fields:
+            _lib.check(_lib.lib.wost_set_models(self._h, None, 0), "WostSolver_2D.set_models")
+            self.models = None
+            return
+        keep = []
+        arr = (_lib.WostModel * len(fields))()
+        for m, (s, a) in enumerate(fields):
+            for name, fld in (("sigma", s), ("alpha", a)):
+                wf, k = _lib.make_field(fld)
+                keep.append(k)
+                setattr(arr[m], name, ctypes.pointer(wf) if wf is not None else None)
+        _lib.check(_lib.lib.wost_set_models(self._h, arr, len(fields)), "WostSolver_2D.set_models")
+        self.models = fields
+
+    @property
+    def num_models(self) -> int:
+        """Models installed by ``set_models`` (0: none)."""
+        n = ctypes.c_int32(0)
+        _lib.check(_lib.lib.wost_models_info(self._h, ctypes.byref(n), None), "wost_models_info")
+        return int(n.value)
+
+    @contextlib.contextmanager
+    def models_installed(self, models):
+        """The models ``models`` (one launch's worth) inside the block; the solver's own models
+        (or none) are restored afterwards."""
+        saved = getattr(self, "models", None)
+        self.set_models(models)
+        try:
+            yield len(models)
+        finally:
+            self.set_models(saved)
+
+    def _solve_models(self, solvePoints, models, sources, k, nWalks, maxSteps, eps, seed, want_walks):
+        """One launch per (model chunk, source chunk, wavenumber chunk) of at most
+        WOST_MAX_SOURCES channels: point sums [M, K, S, N, 3] and (want_walks) per-walk values
+        [M, K, S, N, W]; the solver's models, wavenumbers and source are restored afterwards."""
+        p = _points_np(solvePoints)
+        n = p.shape[0]
+        nWalks = int(nWalks)
+        if nWalks < 1:
+            raise ValueError("nWalks must be >= 1")
+        mods = self.model_fields(models)
+        if not mods:
+            raise ValueError("models must hold at least one (sigma, alpha) pair")
+        if sources is not None and any(is_point_source(s) for s in sources):
+            raise NotImplementedError("solve_models scores source fields: point sources under several models are "
+                                      "not supported")
+        fields = None if sources is None else self.source_fields(sources)
+        kk = None if k is None else np.atleast_1d(np.asarray(k, np.float64)).ravel()
+        if kk is not None and kk.size < 1:
+            raise ValueError("k must hold at least one wavenumber")
+        M, S, K = len(mods), 1 if fields is None else len(fields), 1 if kk is None else kk.size
+        m_chunk, s_chunk, k_chunk = _model_chunks(M, S, K, _lib.WOST_MAX_SOURCES)
+        nb = self.num_blocks(n, nWalks)
+        sums = np.zeros((M, K, S, n, 3), np.float64)
+        vals = np.empty((M, K, S, n, nWalks), np.float32) if want_walks else None
+        steps = None
+        total = None
+        saved_k, saved_m = self.wavenumbers, getattr(self, "models", None)
+        self.set_wavenumbers(None)   # (the setters check models x wavenumbers x sources)
+        self.set_models(None)
+        try:
+            for s0 in range(0, S, s_chunk):
+                s1 = min(S, s0 + s_chunk)
+                with (contextlib.nullcontext() if fields is None else self.sources_installed(fields[s0:s1])):
+                    for m0 in range(0, M, m_chunk):
+                        m1 = min(M, m0 + m_chunk)
+                        try:
+                            self.set_models(mods[m0:m1])
+                            for k0 in range(0, K, k_chunk):
+                                k1 = min(K, k0 + k_chunk)
+                                if kk is not None:
+                                    self.set_wavenumbers(kk[k0:k1])
+                                dm, dk, ds = m1 - m0, k1 - k0, s1 - s0
+                                C = dm * dk * ds
+                                if self.num_channels() != C:   # (the buffers below hold C values per walk)
+                                    raise RuntimeError(f"the handle scores {self.num_channels()} channels, expected {C}")
+                                rows = np.zeros((n, 2 * C + 1), np.float64)
+                                wv = np.empty(n * nWalks * C, np.float32) if want_walks else None
+                                ws = np.empty(n * nWalks, np.uint32) if want_walks else None
+                                _lib.check(_lib.lib.wost_solve_multi(self._h, _lib.fptr(p), n, nWalks, 0, nb,
+                                                                     int(maxSteps), float(eps), int(seed) & (2**64 - 1),
+                                                                     None, _lib.dptr(rows), _lib.fptr(wv),
+                                                                     _lib.u32ptr(ws)), "WostSolver_2D.solve_models")
+                                t = self.timing()
+                                if total is not None:
+                                    for key in _SUMMED_TIMINGS:
+                                        t[key] += total[key]
+                                self.last_timing = total = t
+                                r = rows[:, :2 * C].reshape(n, dm, dk, ds, 2)
+                                sums[m0:m1, k0:k1, s0:s1, :, :2] = r.transpose(1, 2, 3, 0, 4)
+                                sums[m0:m1, k0:k1, s0:s1, :, 2] = rows[:, -1]
+                                if want_walks:
+                                    vals[m0:m1, k0:k1, s0:s1] = wv.reshape(n, nWalks, dm, dk, ds).transpose(2, 3, 4, 0, 1)
+                                    steps = ws.reshape(n, nWalks)
+                        finally:
+                            self.set_wavenumbers(None)
+                            self.set_models(None)
+        finally:
+            self.set_models(saved_m)
+            self.set_wavenumbers(saved_k)
+        return sums, vals, steps
+
+    def solve_models(self, solvePoints, models, nWalks=1000, maxSteps=1000, eps=1e-4, *, sources=None, k=None,
+                     seed: int = 0, return_stats: bool = False):
+        """Shared-path model batching: u[m] is the solve of this problem with the conductivity
+        model ``models[m] = (sigma, alpha)``, every model -- and with ``sources`` / ``k`` every
+        source and wavenumber -- scored by the same walks (``set_models``). Each u[m] is bit
+        for bit the solve of a solver created with that model's fields and
+        ``sigma_bar=self.sigma_bar``, same seed. Returns float32 [M, N], [M, S, N], [M, K, N]
+        or [M, K, S, N]; with ``return_stats`` also a SolveStats whose mean and stderr have
+        that shape. More than WOST_MAX_SOURCES channels are solved in several launches, chosen
+        to be as few as possible and, among those, to keep as many models together as fit
+        (``_model_chunks``); every launch is a walk set of its own, ``last_timing`` sums over
+        them, and the stats' ``total_steps`` counts every walk set that ran (``mean_steps`` is
+        one walk set's). The solver's models, wavenumbers and source are restored afterwards."""
+        sums, _, _ = self._solve_models(solvePoints, models, sources, k, nWalks, maxSteps, eps, seed, False)
+        M, K, S, n = sums.shape[:4]
+        st = stats_from_sums(sums.reshape(M * K * S * n, 3), int(nWalks))
+        shape = (M,) + ((K,) if k is not None else ()) + ((S,) if sources is not None else ()) + (n,)
+        u = st.mean.astype(np.float32).reshape(shape)
+        if not return_stats:
+            return u
+        t = self.last_timing
+        return u, SolveStats(mean=st.mean.reshape(shape), stderr=st.stderr.reshape(shape),
+                             mean_steps=sums[0, 0, 0, :, 2] / int(nWalks), walks=int(nWalks),
+                             total_steps=int(t["total_steps"]), kernel_ms=t["walk_kernel_ms"],
+                             total_ms=t["total_ms"])
+
+    def solve_models_walks(self, solvePoints, models, nWalks=1000, maxSteps=1000, eps=1e-4, *, sources=None,
+                           k=None, seed: int = 0):
+        """Per-walk values of every model (wavenumber, source), float32 [M, N, nWalks] (or
+        [M, K, N, W], [M, S, N, W], [M, K, S, N, W]), and the walks' step counts, uint32
+        [N, nWalks], shared by all channels: the paths do not depend on the model."""
+        _, vals, steps = self._solve_models(solvePoints, models, sources, k, nWalks, maxSteps, eps, seed, True)
+        if sources is None:
+            vals = vals[:, :, 0]
+        if k is None:
+            vals = vals[:, 0]
+        return vals, steps
+
+
+def _model_chunks(M: int, S: int, K: int, cap: int):
+    """(models, sources, wavenumbers) per launch of solve_models for M x S x K channels at
+    most ``cap`` per launch: the split with the fewest launches -- every launch walks the
+    paths once -- and among those the one that keeps the most models together (then sources),
+    so that a model and its background share a walk set whenever that saves one."""
+    best = None
+    for m in range(1, min(M, cap) + 1):
+        for s in range(1, min(S, cap // m) + 1):
+            k = min(K, cap // (m * s))
+            launches = -(-M // m) * -(-S // s) * -(-K // k)
+            key = (launches, -m, -s)
+            if best is None or key < best[0]:
+                best = (key, (m, s, k))
+    return best[1]
 
 
 def _stats_of_multi(sums: np.ndarray, n_walks: int):

@@ -143,6 +143,49 @@ def homogeneous_solver(sc: Scenario, alpha_bg: float, model_solver, **kw):
     return homogeneous(sc, alpha_bg).solver(sigma_bar=model_solver.sigma_bar, **kw)
 
 
+def sigma_bar_for_models(solver, models, k_max: float = 0.0) -> float:
+    """The sigma_bar a solver needs to score ``models`` -- (sigma, alpha) pairs -- with
+    collision weights in [0, 1]: the largest sigma' of any model on the reference's 50 x 50
+    grid over the domain's bounding box (buildModifiedSigma's grid, as
+    ``wavenumber.sigma_bar_for``) plus k_max^2. ``solver``: a WostSolver_2D of the problem
+    with delta tracking (any sigma_bar). Each model is installed alone (``set_models``: the
+    solver then evaluates that model's fields, ``eval_field``); the solver's own models are
+    restored afterwards."""
+    from .scenarios import torch_linspace
+
+    if not solver.use_delta_tracking:
+        raise NotImplementedError("models need delta tracking: create the solver with sigma or alpha")
+    (x0, x1), (y0, y1) = solver.domain_bounds
+    gx, gy = np.meshgrid(torch_linspace(x0, x1, 50), torch_linspace(y0, y1, 50), indexing="ij")
+    grid = np.stack([gx.ravel(), gy.ravel()], axis=1)
+    top = None
+    for model in models:
+        with solver.models_installed([model]):
+            sp = solver.eval_field("sigma_prime", grid)[:, 0].astype(np.float64)
+        sp = sp[np.isfinite(sp)]
+        if sp.size:
+            top = float(sp.max()) if top is None else max(top, float(sp.max()))
+    if top is None:
+        raise ValueError("sigma' could not be evaluated at any grid point of any model")
+    return max(top, 0.0) + float(k_max) ** 2
+
+
+def paired_difference(walks: np.ndarray):
+    """Paired differences between models solved on shared paths: from per-walk values
+    [M, N, W] (``WostSolver_2D.solve_models_walks``: walk w of point n is the same path in
+    every model) returns (mean, stderr), each [M, N]: the mean of v_m - v_0 over the walks
+    and its standard error from the per-walk differences (row 0 is exactly 0). The common
+    part of the noise cancels walk by walk, which two separate solves cannot do."""
+    v = np.asarray(walks, np.float64)
+    if v.ndim != 3:
+        raise ValueError(f"walks must have shape [M, N, W], got {v.shape}")
+    d = v - v[:1]
+    w = v.shape[2]
+    mean = d.mean(axis=2)
+    var = ((d - mean[:, :, None]) ** 2).sum(axis=2) / max(w - 1, 1)
+    return mean, np.sqrt(var / w)
+
+
 def paired_apparent_resistivity(model_walks: np.ndarray, bg_walks: np.ndarray, pairs: np.ndarray,
                                 rho_bg: float) -> ApparentResistivity:
     """rho_a from per-walk values [E, W] of the model and the background solved on
@@ -487,17 +530,34 @@ class SurveyResult:
     walk_steps: int
 
 
+def _model_and_background(sc: Scenario, alpha_bg: float):
+    """The two models of a shared-walk survey: the scenario's fields and homogeneous()'s."""
+    return [(sc.sigma, sc.alpha), (sc.sigma, F.const(alpha_bg))]
+
+
 def run_dipole_dipole(sc: Scenario, alpha_bg: float, n_walks: int, seed: int = 0, device: int | None = None,
-                      solvers=None) -> SurveyResult:
+                      solvers=None, shared_walks: bool = False) -> SurveyResult:
     """Solve the survey on the GPU: electrode potentials of the model and of the
-    homogeneous background (same walk streams), then dV and rho_a = (1/alpha_bg) dV/dV_bg."""
+    homogeneous background (same walk streams), then dV and rho_a = (1/alpha_bg) dV/dV_bg.
+    shared_walks: model and background as two models of one solver and one walk set
+    (WostSolver_2D.solve_models) instead of two solves on one sigma_bar and seed: every
+    array of the result is bitwise the same, walk_steps counts the one walk set.
+    ``solvers`` is then the model solver (or a tuple whose first entry it is)."""
+    pairs = dipole_dipole_pairs(len(sc.points))
+    if shared_walks:
+        sm = sc.solver(device=device) if solvers is None else (solvers[0] if isinstance(solvers, tuple) else solvers)
+        _, st = sm.solve_models(sc.points, _model_and_background(sc, alpha_bg), nWalks=n_walks,
+                                maxSteps=sc.max_steps, eps=sc.eps, seed=seed, return_stats=True)
+        dm = potential_differences(st.mean[0], st.stderr[0], pairs)
+        dh = potential_differences(st.mean[1], st.stderr[1], pairs)
+        return SurveyResult(pairs, dm, dh, apparent_resistivity(dm, dh, 1.0 / alpha_bg), st.mean[0], st.mean[1],
+                            st.total_steps)
     if solvers is None:
         sm = sc.solver(device=device)
         solvers = (sm, homogeneous_solver(sc, alpha_bg, sm, device=device))
     sm, sh = solvers
     _, st_m = sm.solve(sc.points, nWalks=n_walks, maxSteps=sc.max_steps, eps=sc.eps, seed=seed, return_stats=True)
     _, st_h = sh.solve(sc.points, nWalks=n_walks, maxSteps=sc.max_steps, eps=sc.eps, seed=seed, return_stats=True)
-    pairs = dipole_dipole_pairs(len(sc.points))
     dm = potential_differences(st_m.mean, st_m.stderr, pairs)
     dh = potential_differences(st_h.mean, st_h.stderr, pairs)
     return SurveyResult(pairs, dm, dh, apparent_resistivity(dm, dh, 1.0 / alpha_bg), st_m.mean, st_h.mean,
@@ -532,23 +592,39 @@ class MultiSurveyResult:
 
 
 def run_dipole_dipole_survey(sc: Scenario, alpha_bg: float, n_walks: int, n_max: int = 4, width: float = 0.5,
-                             seed: int = 0, device: int | None = None, solvers=None) -> MultiSurveyResult:
+                             seed: int = 0, device: int | None = None, solvers=None,
+                             shared_walks: bool = False) -> MultiSurveyResult:
     """A full dipole-dipole pseudosection: one transmitter dipole (c, c+1) per
     electrode pair, every electrode's potential for each, model and homogeneous
     background. All transmitters are scored by the same walks
     (WostSolver_2D.solve_sources: the walks do not depend on the source), so the
-    survey costs two walk sets per electrode instead of two per transmitter."""
+    survey costs two walk sets per electrode instead of two per transmitter.
+    shared_walks: model and background as two models of one solver
+    (WostSolver_2D.solve_models: sources x 2 models per walk, 16 channels per launch). Up
+    to 8 transmitters that is one walk set instead of two; beyond, both paths need
+    ceil(2 T / 16) launches or one more, and model and background still share each launch's
+    paths. Every array of the result is bitwise the same; walk_steps counts every walk set
+    that ran. ``solvers`` is then the model solver (or a tuple whose first entry it is)."""
     E = len(sc.points)
     quad = dipole_dipole_quadripoles(E, n_max)
     tx = np.unique(quad[:, :2], axis=0) if len(quad) else np.zeros((0, 2), np.int64)
     srcs = [dipole_source(sc.points[a], sc.points[b], width) for a, b in tx]
-    if solvers is None:
-        sm = sc.solver(device=device)
-        solvers = (sm, homogeneous_solver(sc, alpha_bg, sm, device=device))
-    sm, sh = solvers
     out = []
     steps = 0
-    for s in (sm, sh):
+    if shared_walks:
+        sm = sc.solver(device=device) if solvers is None else (solvers[0] if isinstance(solvers, tuple) else solvers)
+        if srcs:
+            _, st = sm.solve_models(sc.points, _model_and_background(sc, alpha_bg), nWalks=n_walks,
+                                    maxSteps=sc.max_steps, eps=sc.eps, sources=srcs, seed=seed, return_stats=True)
+            out = [(st.mean[0], st.stderr[0]), (st.mean[1], st.stderr[1])]
+            steps = st.total_steps
+        else:
+            out = [(np.zeros((0, E)), np.zeros((0, E)))] * 2
+        solvers = ()
+    elif solvers is None:
+        sm = sc.solver(device=device)
+        solvers = (sm, homogeneous_solver(sc, alpha_bg, sm, device=device))
+    for s in solvers:
         if not srcs:
             out.append((np.zeros((0, E)), np.zeros((0, E))))
             continue

@@ -312,8 +312,43 @@ int wost_solve_multi(wost_handle* h, const float* points, int64_t n_points,
  * clamps each channel's weight at 0 as the reference does; compat="fixed" keeps it signed
  * (unbiased for any sigma_bar, at a higher variance when the bound is violated). */
 int wost_set_wavenumbers(wost_handle* h, const double* k2, int32_t n);
-/* Values a solve of the handle scores per walk: max(1, wavenumbers) * wost_num_sources. */
+/* Values a solve of the handle scores per walk: max(1, models) * max(1, wavenumbers) *
+ * wost_num_sources. */
 int wost_num_channels(const wost_handle* h, int32_t* n_channels);
+
+/* Shared-path model batching (no reference counterpart). Under delta tracking a
+ * walk's path depends only on sigma_bar and the geometry: the conductivity enters a step
+ * through alpha_jet(y) and sigma(y) (the collision weight 1 - sigma'/sigma_bar), alpha(next) /
+ * alpha(x) (the factor sqrt(a_new / alpha(x))), rsq(alpha(y) alpha(x)) in the source score, and
+ * alpha at the walk's start. So one walk can carry one weight per (sigma, alpha) pair and score
+ * n conductivity models: a survey's model and its homogeneous background, or a model and its
+ * perturbations for paired differences, for one set of walks.
+ * wost_set_models gives the handle n models (n = 0: back to the problem's own fields). A model's
+ * NULL field follows wost_problem's rules (sigma NULL: 0, alpha NULL: the constant 1). Solves
+ * then score C = n * max(1, wavenumbers) * S channels per walk, channel c = (m * K + j) * S + s
+ * (model m major, then wavenumber j, then source s). wost_solve_multi, wost_solve_range and
+ * wost_solve_distributed take C wherever they document S (wost_solve_distributed's ranks also
+ * agree on the models' checksum); wost_solve and wost_solve_history need C == 1. Each channel's
+ * sums are bit for bit those of a single solve of a handle created with model m's fields and
+ * this handle's sigma_bar, which stays the one fixed at wost_create: create the handle with
+ * sigma_bar_override >= the largest sigma' of any model. With n = 1 the handle runs the kernel
+ * of a handle created with that model's fields (wost_eval_field then evaluates them); n >= 2
+ * needs the field-specialised kernel, never races its compile, and tree launches run without
+ * walk pools, as with several wavenumbers.
+ *   WOST_ERR_INVALID_ARG  a model with both fields NULL; n * wavenumbers * S > WOST_MAX_SOURCES
+ *                         (wost_set_sources and wost_set_wavenumbers check the same product);
+ *   WOST_ERR_UNSUPPORTED  a handle without delta tracking; n >= 2 with the field-specialised
+ *                         kernel disabled (reported by the solve); n >= 2 together with point
+ *                         charges, from whichever of wost_set_models / wost_set_point_sources
+ *                         comes second (the charge buffer holds one alpha(z_p) per charge). */
+typedef struct {
+    const wost_field* sigma;
+    const wost_field* alpha;
+} wost_model;
+int wost_set_models(wost_handle* h, const wost_model* models, int32_t n);
+/* The handle's model count and the FNV-1a 64 checksum of their converted fields (0, 0 when
+ * none is set); either pointer may be NULL. */
+int wost_models_info(const wost_handle* h, int32_t* n, uint64_t* checksum);
 
 /* Point sources (compat="fixed"; no reference counterpart). A DC survey injects
  * current at points. With f = sum_p q_p delta(z_p) the source integral of a Walk-on-Stars
@@ -583,6 +618,13 @@ int wost_kernel_source_sources(const wost_problem* problem, const wost_field* co
  * multi-wavenumber kernel. */
 int wost_kernel_source_channels(const wost_problem* problem, const wost_field* const* sources, int32_t n_sources,
                                 int32_t n_wavenumbers, char* out, int64_t capacity, int64_t* length);
+
+/* The same for n_models models on top (wost_set_models; 0: none, the bytes of
+ * wost_kernel_source_channels; 1: those of a problem that carries that model's fields).
+ * Host only. */
+int wost_kernel_source_models(const wost_problem* problem, const wost_model* models, int32_t n_models,
+                              const wost_field* const* sources, int32_t n_sources, int32_t n_wavenumbers,
+                              char* out, int64_t capacity, int64_t* length);
 
 /* The same for a handle with n_charges point charges in n_sources source channels
  * (wost_set_point_sources; the problem must have no source field) and n_wavenumbers
