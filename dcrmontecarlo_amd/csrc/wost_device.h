@@ -1043,23 +1043,11 @@ WOST_HD float bits_to_float(int32_t b) { return __builtin_bit_cast(float, b); }
 // r = a - q dn (exact, fma), RN(q + r y) -- correctly rounded for every a with
 // 2^-100 <= |a| <= 2 and each of these 65 dn, checked exhaustively on the host
 // (tests/native/unit_dir_check.cpp). Anything else takes the IEEE operations.
-// (n, y) of unit_direction for k = -64..64 (A/B WOST_EXP_UNIT_TAB: one load instead of
-// the bit arithmetic)
-struct UnitDirTab { float v[2 * 129]; };
-constexpr UnitDirTab make_unit_dir_tab() {
-    UnitDirTab t{};
-    for (int k = -64; k <= 64; ++k) {
-        const int32_t kneg = k >> 31, j = ((k >> 1) & ~kneg) | (-((1 - k) >> 1) & kneg);
-        const int32_t jneg = j >> 31;
-        t.v[2 * (k + 64)] = __builtin_bit_cast(float, 0x3F800000 + j);
-        t.v[2 * (k + 64) + 1] = __builtin_bit_cast(float, 0x3F800000 + ((-2 * j) & ~jneg) + (((1 - j) >> 1) & jneg));
-    }
-    return t;
-}
-#if defined(WOST_EXP_UNIT_TAB) && defined(__HIP_DEVICE_COMPILE__)
-__constant__ UnitDirTab kUnitDirTab = make_unit_dir_tab();
-#endif
-
+// Both j are floor(k/2), so with B the bit pattern of 1 the two patterns are
+//   bits(dn) = B + j = (bits(s2) + B) >> 1      (a logical shift; 2B + k is positive),
+//   bits(y)  = B - max(2j, j >> 1)              (2j for j >= 0, floor(j/2) = -ceil(-j/2) else),
+// a handful of integer operations without a select. (A table of the 129 pairs saved as
+// many instructions but put an LDS load and its wait in the chain: +0.4%, round 5.)
 WOST_HD void unit_direction(float dxi, float dyi, float& dn, float& dx, float& dy) {
 #pragma clang fp contract(off)
     const float s2 = dxi * dxi + dyi * dyi;
@@ -1069,17 +1057,12 @@ WOST_HD void unit_direction(float dxi, float dyi, float& dn, float& dx, float& d
 #else
     const bool fast = (uint32_t)(k + 64) <= 128u && fabsf(dxi) >= 0x1p-100f && fabsf(dyi) >= 0x1p-100f;
 #endif
-#if defined(WOST_EXP_UNIT_TAB) && defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t ti = (uint32_t)(k + 64) <= 128u ? (uint32_t)(k + 64) : 64u;
-    const float2 nyv = reinterpret_cast<const float2*>(kUnitDirTab.v)[ti];
-    const float n = nyv.x, y = nyv.y;
-#else
-    // branch-free selects (the compiler otherwise splits the wave here)
-    const int32_t kneg = k >> 31, j = ((k >> 1) & ~kneg) | (-((1 - k) >> 1) & kneg);
-    const int32_t jneg = j >> 31;
-    const float n = bits_to_float(0x3F800000 + j);
-    const float y = bits_to_float(0x3F800000 + ((-2 * j) & ~jneg) + (((1 - j) >> 1) & jneg));
-#endif
+    // (the patterns of a lane that is not fast are not used; unsigned where its j would overflow)
+    const int32_t nb = (int32_t)((__builtin_bit_cast(uint32_t, s2) + 0x3F800000u) >> 1);
+    const int32_t j = nb - 0x3F800000;
+    const int32_t j2 = (int32_t)((uint32_t)j << 1), jh = j >> 1;
+    const float n = bits_to_float(nb);
+    const float y = bits_to_float(0x3F800000 - (j2 > jh ? j2 : jh));
     const float qx = dxi * y, qy = dyi * y;
     dn = n;
     dx = fmaf(fmaf(-qx, n, dxi), y, qx);

@@ -731,7 +731,6 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
     if (xf & 65536) o << "#define WOST_ABL_NO_SILHOUETTE 1\n";
     if (xf & 64) o << "#define WOST_EXP_PARTIAL_UNROLL 1\n";
     if (xf & 128) o << "#define WOST_EXP_LIBM_SINCOS 1\n";
-    if (xf & (1 << 29)) o << "#define WOST_EXP_UNIT_TAB 1\n";   // A/B: unit_direction's (n, y) table
     if (xf & 131072) o << "#define WOST_EXP_SCAN_BITS 1\n";   // A/B: neumann_scan_both's per-vertex bits
     if ((xf >> 18) & 1023) o << "#define WOST_ABL_DUP " << ((xf >> 18) & 1023) << "\n";   // phase_dup.sh
     o << "#define WOST_JIT_TRIG_EXACT " << (v.exact_trig ? 1 : 0) << "\n";   // wost_set_trig
