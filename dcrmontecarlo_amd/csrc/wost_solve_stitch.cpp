@@ -1,0 +1,254 @@
+// wost_solve_stitch.cpp -- the wost_solve* entry points, and the solves they stitch from
+// several solve_impl calls: wost_solve_range beyond one launch per point, and the solve
+// that starts on the precompiled kernel while its own compiles (option jit_race).
+#include <algorithm>
+#include <chrono>
+
+#include "wost_handle.h"
+
+using namespace wost;
+
+namespace {
+
+SolveRequest whole_request(const float* points, int64_t n_points, int64_t W, int32_t max_steps, float eps,
+                           uint64_t seed) {
+    return SolveRequest{.points = points, .n_points = n_points, .W = W, .max_steps = max_steps, .eps = eps,
+                        .seed = seed, .block_end = wost_num_blocks(n_points, W)};
+}
+
+// Accumulates a piece's timing into a multi-launch solve's (wost_solve_range, solve_race).
+void add_timing(wost_timing& acc, const wost_timing& t) {
+    acc.walk_kernel_ms += t.walk_kernel_ms;
+    acc.reduce_kernel_ms += t.reduce_kernel_ms;
+    acc.total_ms += t.total_ms;
+    acc.n_launches += t.n_launches;
+    acc.total_steps += t.total_steps;
+    acc.total_walks += t.total_walks;
+    acc.grid_blocks = t.grid_blocks;
+    acc.jit = t.jit;
+    acc.tree = t.tree;
+    acc.blocks_per_cu = t.blocks_per_cu;
+    acc.block_threads = t.block_threads;
+    acc.chunk0 = t.chunk0;
+    acc.chunk = t.chunk;
+    acc.adaptive = t.adaptive;
+    acc.max_walk_steps = std::max(acc.max_walk_steps, t.max_walk_steps);
+    acc.jit_ms += t.jit_ms;
+    acc.span_ms += t.span_ms;
+    acc.tail_ms = t.tail_ms;
+    acc.last_wave_ms = t.last_wave_ms;
+    acc.last_wave_iters = t.last_wave_iters;
+    acc.max_wave_iters = std::max(acc.max_wave_iters, t.max_wave_iters);
+    acc.precompiled_walks += t.precompiled_walks;
+}
+
+// A solve of walks [w_begin, w_begin + Wr) of every point that takes several solves of
+// block-aligned sub-ranges (wost_solve_range beyond one launch per point, solve_race): each
+// piece's block rows, values and steps are scattered into the whole range's layout, so the
+// block sums, their order and every output are those of one solve.
+struct Stitch {
+    SolveRequest rq;       // the whole solve (its ranges set per piece)
+    SolveOutputs out;
+    int ns = 1;            // values per walk
+    int64_t w_begin = 0, Wr = 0, nbr = 0;
+    std::vector<double> all, part;   // block rows of the range / of a piece
+    std::vector<float> pv;
+    std::vector<uint32_t> ps;
+    wost_timing acc{};
+    double solve_ms = 0.0;   // host time of the last piece's solve
+
+    Stitch(const SolveRequest& whole, const SolveOutputs& o, int ns_, int64_t w0, int64_t w1)
+        : rq(whole), out(o), ns(ns_), w_begin(w0), Wr(w1 - w0), nbr((w1 - w0 + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS),
+          all((size_t)whole.n_points * nbr * (2 * ns_ + 1)) {}
+};
+
+// Solves walks [c0, c1) of every point into the stitched solve's outputs and timing.
+int solve_piece(wost_handle* h, Stitch& s, int64_t c0, int64_t c1) {
+    const int row = 2 * s.ns + 1;
+    const int64_t n_points = s.rq.n_points;
+    const int64_t wc = c1 - c0, nbc = (wc + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
+    const int64_t woff = c0 - s.w_begin, boff = woff / WOST_BLOCK_WALKS;
+    s.part.resize((size_t)n_points * nbc * row);
+    if (s.out.walk_values) s.pv.resize((size_t)n_points * wc * s.ns);
+    if (s.out.walk_steps) s.ps.resize((size_t)n_points * wc);
+    // (the whole of [0, W) is an ordinary solve of every block: solve_impl takes it as no range)
+    s.rq.walk_begin = c0;
+    s.rq.walk_end = c1;
+    SolveOutputs piece;
+    piece.block_stats = s.part.data();
+    piece.walk_values = s.out.walk_values ? s.pv.data() : nullptr;
+    piece.walk_steps = s.out.walk_steps ? s.ps.data() : nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = solve_impl(h, s.rq, piece);
+    s.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != WOST_OK) return rc;
+    for (int64_t p = 0; p < n_points; ++p) {
+        std::memcpy(&s.all[((size_t)p * s.nbr + boff) * row], &s.part[(size_t)p * nbc * row], sizeof(double) * nbc * row);
+        if (s.out.walk_values)
+            std::memcpy(s.out.walk_values + ((size_t)p * s.Wr + woff) * s.ns, &s.pv[(size_t)p * wc * s.ns],
+                        sizeof(float) * wc * s.ns);
+        if (s.out.walk_steps)
+            std::memcpy(s.out.walk_steps + (size_t)p * s.Wr + woff, &s.ps[(size_t)p * wc], sizeof(uint32_t) * wc);
+    }
+    add_timing(s.acc, h->timing);
+    return WOST_OK;
+}
+
+// The stitched solve's block rows and point sums (in the range's block order) to the caller.
+void stitched_stats(const Stitch& s) {
+    const int row = 2 * s.ns + 1;
+    if (s.out.block_stats) std::memcpy(s.out.block_stats, s.all.data(), sizeof(double) * s.all.size());
+    if (!s.out.point_stats) return;
+    std::fill(s.out.point_stats, s.out.point_stats + (size_t)row * s.rq.n_points, 0.0);
+    for (int64_t p = 0; p < s.rq.n_points; ++p)
+        for (int64_t k = 0; k < s.nbr; ++k)
+            for (int c = 0; c < row; ++c) s.out.point_stats[(size_t)row * p + c] += s.all[((size_t)p * s.nbr + k) * row + c];
+}
+
+// A whole single-source solve whose field-specialised kernel is in no cache (option
+// jit_race; the reference calls solve() once per script): its compile starts in a helper
+// process, and meanwhile the precompiled kernel -- the same bits walk for walk
+// (test_jit_kernel_matches_interpreted_kernel) but 2-5x slower -- runs the walks in ranges
+// of every point (the first ~2^19 walks, then ~16 ms of work each); once the compile is
+// done the specialised kernel runs the rest. Ranges of walks are whole blocks, so the
+// block sums, their order and every output are those of one launch (as wost_solve_range's).
+// A solve that finds the compile already running waits for it instead (jit_get_kernel).
+constexpr double kCompileExpectMs = 300.0;   // a specialised kernel's compile (MI355X box: 180-600 ms)
+
+int solve_race(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out) {
+    const float* points = rq.points;
+    const int64_t n_points = rq.n_points, W = rq.W;
+    if (!points) return solve_impl(h, rq, out);
+    for (int64_t i = 0; i < 2 * n_points; ++i)
+        if (!std::isfinite(points[i])) return solve_impl(h, rq, out);   // (its error message)
+    const WalkTraits t = walk_traits(h);
+    if (t.delta && !h->fields[SLOT_F].present) return solve_impl(h, rq, out);
+    HIP_TRY(hipSetDevice(h->device));
+    int rc;
+    if ((rc = upload_program(h)) != WOST_OK) return rc;
+    if (t.tree && (rc = ensure_tree(h)) != WOST_OK) return rc;
+    KernelShape ks;
+    if ((rc = first_kernel_shape(h, t, &ks)) != WOST_OK) return rc;
+    JitTicket ticket;
+    if (jit_kernel_try(h, kernel_variant(h, t, ks, false, 1), &ticket) != JitTry::kStarted)
+        return solve_impl(h, rq, out);
+
+    const int64_t max_piece = kMaxBatchWalks / WOST_BLOCK_WALKS * WOST_BLOCK_WALKS;   // walks of a point per launch
+    auto blocks_up = [](double walks) {
+        const double b = std::ceil(std::max(walks, 1.0) / WOST_BLOCK_WALKS);
+        return (int64_t)std::min(b, 1e15) * WOST_BLOCK_WALKS;
+    };
+    int64_t piece = std::min(max_piece, blocks_up((double)(1 << 19) / (double)n_points));
+    const auto race_t0 = std::chrono::steady_clock::now();
+    Stitch st(rq, out, 1, 0, W);
+    bool jit_now = false;
+    const bool saved = h->jit_enabled;
+    for (int64_t w0 = 0; w0 < W;) {
+        if (!jit_now && ticket.done()) jit_now = true;
+        const int64_t w1 = std::min(W, w0 + (jit_now ? max_piece : piece));
+        const int64_t wc = w1 - w0;
+        h->jit_enabled = jit_now;
+        rc = solve_piece(h, st, w0, w1);
+        h->jit_enabled = saved;
+        if (rc == WOST_ERR_UNSUPPORTED && !jit_now) {   // (a shape only the specialised kernel runs)
+            jit_now = true;
+            continue;
+        }
+        if (rc != WOST_OK) return rc;
+        if (!jit_now) {
+            st.acc.precompiled_walks += (uint64_t)(n_points * wc);
+            // the next range, from this one's rate: all the rest when the precompiled kernel
+            // finishes it before the compile is likely done (every range ends in a tail of
+            // the longest walks: one launch, not many); else about half the compile's
+            // expected remaining time, at least 16 ms of work, at most 8x this range
+            const double rate = (double)wc / std::max(st.solve_ms, 0.05);   // walks per point per ms
+            const double since = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() -
+                                                                            race_t0).count();
+            const double compile_left = std::max(0.0, kCompileExpectMs - since);
+            if ((double)(W - w1) / rate <= compile_left) {
+                piece = std::min(max_piece, W - w1);
+            } else {
+                const double target = std::max(16.0, 0.5 * compile_left);
+                piece = std::min(max_piece, std::max(piece, std::min(8 * piece, blocks_up(rate * target))));
+            }
+        }
+        w0 = w1;
+    }
+    stitched_stats(st);
+    st.acc.jit = jit_now ? 1 : 0;
+    h->timing = st.acc;
+    return WOST_OK;
+}
+
+// The entry points' output pointers.
+SolveOutputs outputs(double* block_stats, double* point_stats, float* walk_values, uint32_t* walk_steps,
+                     float* records = nullptr) {
+    return SolveOutputs{.block_stats = block_stats, .point_stats = point_stats, .walk_values = walk_values,
+                        .walk_steps = walk_steps, .records = records};
+}
+
+}  // namespace
+
+extern "C" {
+
+int wost_solve(wost_handle* h, const float* points, int64_t n_points, int64_t W,
+               int64_t block_begin, int64_t block_end, int32_t max_steps, float eps, uint64_t seed,
+               double* block_stats, double* point_stats, float* walk_values, uint32_t* walk_steps) {
+    SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
+    const SolveOutputs out = outputs(block_stats, point_stats, walk_values, walk_steps);
+    // a whole single-source solve may start on the precompiled kernel while its specialised
+    // one compiles (solve_race)
+    if (h && h->jit_enabled && h->opt.jit_race && h->channels() == 1 && h->charges.empty() && n_points > 0 && W > 0 &&
+        block_begin == 0 &&
+        block_end == rq.block_end && max_steps >= 0 && eps == eps)
+        return solve_race(h, rq, out);
+    rq.block_begin = block_begin;
+    rq.block_end = block_end;
+    return solve_impl(h, rq, out);
+}
+
+int wost_solve_range(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t walk_begin,
+                     int64_t walk_end, int32_t max_steps, float eps, uint64_t seed, double* block_stats,
+                     double* point_stats, float* walk_values, uint32_t* walk_steps) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
+    rq.multi = true;
+    const SolveOutputs out = outputs(block_stats, point_stats, walk_values, walk_steps);
+    if (walk_begin == 0 && walk_end == W) return solve_impl(h, rq, out);   // the whole range: an ordinary solve
+    const int ns = h->channels();
+    const int64_t chunk = (kMaxBatchWalks / ns) / WOST_BLOCK_WALKS * WOST_BLOCK_WALKS;   // walks of a point per launch
+    if (walk_end - walk_begin <= chunk || walk_begin < 0 || walk_end <= walk_begin || n_points <= 0) {
+        rq.block_end = 0;   // (a range names its walks only)
+        rq.walk_begin = walk_begin;
+        rq.walk_end = walk_end;
+        return solve_impl(h, rq, out);
+    }
+    // a range longer than one launch holds per point: block-aligned sub-ranges, one solve
+    // each, scattered into the range's layout; point sums in the range's block order
+    Stitch st(rq, out, ns, walk_begin, walk_end);
+    for (int64_t c0 = walk_begin; c0 < walk_end; c0 += chunk)
+        if (int rc = solve_piece(h, st, c0, std::min(walk_end, c0 + chunk))) return rc;
+    stitched_stats(st);
+    h->timing = st.acc;
+    return WOST_OK;
+}
+
+int wost_solve_history(wost_handle* h, const float* points, int64_t n_points, int64_t W, int32_t max_steps,
+                       float eps, uint64_t seed, double* point_stats, float* walk_values, uint32_t* walk_steps,
+                       float* records) {
+    if (!records) return fail(WOST_ERR_INVALID_ARG, "NULL records");
+    return solve_impl(h, whole_request(points, n_points, W, max_steps, eps, seed),
+                      outputs(nullptr, point_stats, walk_values, walk_steps, records));
+}
+
+int wost_solve_multi(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t block_begin,
+                     int64_t block_end, int32_t max_steps, float eps, uint64_t seed, double* block_stats,
+                     double* point_stats, float* walk_values, uint32_t* walk_steps) {
+    SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
+    rq.multi = true;
+    rq.block_begin = block_begin;
+    rq.block_end = block_end;
+    return solve_impl(h, rq, outputs(block_stats, point_stats, walk_values, walk_steps));
+}
+
+}  // extern "C"

@@ -19,14 +19,14 @@ static uint64_t g_corrected[3][2];   // [path: range, small32, 64-bit][--q, ++q]
 using namespace wost;
 
 constexpr int64_t B = WOST_BLOCK_WALKS;
-constexpr int64_t kBatchLimit = int64_t(1) << 26;   // wost_api.hip kMaxBatchWalks
+constexpr int64_t kBatchLimit = int64_t(1) << 26;   // wost_handle.h kMaxBatchWalks
 
 static long fails = 0;
 static uint64_t g_checked[3];    // indices checked per path
 static uint64_t g_batches[3];
 #define CHECK(c) do { if (!(c)) { if (fails < 20) std::fprintf(stderr, "check failed: %s (line %d)\n", #c, __LINE__); ++fails; } } while (0)
 
-// The id fields of the kernel's arguments, as wost_api.hip fill_walk_args / set_batch_args set them.
+// The id fields of the kernel's arguments, as wost_solve.cpp fill_walk_args / set_batch_args set them.
 static WalkArgs args_of(const SolveRanges& r, const Batch& b) {
     WalkArgs a{};
     a.walks_per_point = r.W;

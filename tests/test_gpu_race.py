@@ -1,5 +1,5 @@
-"""A solve whose field-specialised kernel is in no cache (option jit_race, wost_api.hip
-solve_race): the kernel compiles in a helper process while the precompiled kernel runs the
+"""A solve whose field-specialised kernel is in no cache (option jit_race,
+wost_solve_stitch.cpp solve_race): the kernel compiles in a helper process while the precompiled kernel runs the
 walks in ranges of every point, and the specialised kernel takes over the rest once it is
 ready. Each walk's value and step count depend only on (seed, walk id), and the two
 kernels compute every walk bit for bit alike (test_jit_kernel_matches_interpreted_kernel),

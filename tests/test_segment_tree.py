@@ -45,7 +45,7 @@ def harness(tmp_path_factory):
 
 
 def stop2_of(rmin):
-    """The largest float32 whose (correctly rounded) sqrt is <= rmin (wost_api.hip silhouette_stop2)."""
+    """The largest float32 whose (correctly rounded) sqrt is <= rmin (wost_solve.cpp silhouette_stop2)."""
     rmin = np.float32(rmin)
     x = np.float32(rmin * rmin)
     while x > 0 and np.sqrt(x) > rmin:
@@ -286,7 +286,7 @@ def test_tree_nearest_crossing_matches_scan(harness, leaf):
 def test_tree_depth_limit(harness):
     """The traversals keep 4 pending-child bits per level in 32 bits (wost_tree.h
     kTreeMaxDepth = 8): the builder refuses a deeper tree, and libwost then retries with
-    32-segment leaves (wost_api.hip ensure_tree) before failing loudly."""
+    32-segment leaves (wost_resources.cpp ensure_tree) before failing loudly."""
     n = 65536 + 2   # 65537 segments: 4^8 one-segment leaves are one too few
     x = np.linspace(-1.0, 1.0, n, dtype=np.float32)
     xy = np.ascontiguousarray(np.stack([x, np.sin(x)], 1), np.float32)

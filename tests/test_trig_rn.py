@@ -18,7 +18,7 @@ REPO = os.path.dirname(HERE)
 
 
 def segment_phi(V):
-    """atan2 of each segment's left normal, as wost_api.hip computes it on the host (the C
+    """atan2 of each segment's left normal, as wost_program.cpp segment_angles computes it on the host (the C
     library's atan2f, which torch.atan2 of the reference's 0-d tensors calls)."""
     libm = ctypes.CDLL("libm.so.6")
     libm.atan2f.argtypes = [ctypes.c_float, ctypes.c_float]
