@@ -184,6 +184,8 @@ def _load():
                                                  ctypes.c_char_p, c_int64, POINTER(c_int64)]),
         "wost_kernel_source_channels": (c_int32, [POINTER(WostProblem), POINTER(POINTER(WostField)), c_int32, c_int32,
                                                   ctypes.c_char_p, c_int64, POINTER(c_int64)]),
+        "wost_kernel_source_options": (c_int32, [POINTER(WostProblem), POINTER(c_char_p), POINTER(c_double), c_int32,
+                                                 ctypes.c_char_p, c_int64, POINTER(c_int64)]),
         "wost_jit_compile": (c_int32, [ctypes.c_char_p, ctypes.c_char_p, c_int32, POINTER(c_uint8), c_int64,
                                        POINTER(c_int64), POINTER(c_int32)]),
         "wost_eval_field": (c_int32, [H, c_int32, POINTER(c_float), c_int64, POINTER(c_float)]),

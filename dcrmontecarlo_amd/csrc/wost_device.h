@@ -730,6 +730,46 @@ WOST_HD float sigma_prime_from(const Jet& alpha, float sigma, bool detached) {
     return ratio + 0.5f * (f_div(lap, ac) - gn / 2.0f);
 }
 
+// ---- sigma' at a flat alpha jet (the specialised kernels' collision weight) ----
+// A kernel whose sigma is the constant 0 scales a colliding walk's weight by
+//   sc = 1 - sigma'(y) / sigma_bar,  sigma' = sigma_prime_from({a, z, z, z}, 0, false),
+// and on the whole-field saturated return (above) z = 0. The call then evaluates, with
+// y = rcp(a) (v_rcp_f32: within 1 ulp of 1/a) and every operation rounded to nearest,
+//   ac = a (a >= 1e-8: not clamped), ratio = 0 * y = 0, gx = gy = 0, lap = 1e-8f + 0,
+//   lx = ly = 0 * rden = 0 (rden = rcp(a) or rcp(a + 1e-8f), finite or 0), gn = 0,
+//   sigma' = 0 + 0.5f * (1e-8f * y - 0 / 2) = 0.5f * RN(1e-8f * y)       (the halving is exact),
+//   sc = 1.0f - sigma' * inv_sb  (fused or not; max(0, .) leaves a value >= 0 alone).
+// 1.0f - p is 1.0f for every |p| <= 2^-25: below 1 the floats are 2^-24 apart, so p <= 2^-25
+// is at most the half-way point, which rounds to the even 1.0f; above 1 they are 2^-23
+// apart (a negative inv_sb). A separately rounded product RN(p) <= 2^-25 whenever p <= 2^-25.
+// With y <= (1/a)(1 + 2^-23)(1 + 2^-24) -- the neighbour above RN(1/a) -- and one more
+// rounding in 1e-8f * y,
+//   |p| <= 0.5 * 1e-8f * |inv_sb| / a * (1 + 2^-22),   1e-8f = 0x1.5798eep-27 < 1.0000000e-8,
+// so |p| <= 2^-25 holds for a >= 0.5e-8 * 2^25 * (1 + 2^-22) |inv_sb| = 0.16777220 |inv_sb|.
+// kFlatAlphaC = 0.1678 keeps a margin of 1.6e-4 over that, which also covers the rounding
+// of the bound's own product (2^-24) and a subnormal 1e-8f * y (absolute error 2^-149, times
+// |inv_sb| <= 2^64: nothing). flat_alpha_min is formed once per kernel; a lane is trivial
+// when its jet is the flat one and alpha.v >= flat_alpha_min:
+//  * the bound is at least 1e-8f, so a trivial alpha is never clamped;
+//  * |inv_sb| above 2^64, infinite or NaN gives a NaN bound, and no lane is trivial;
+//  * a NaN alpha fails the comparison; alpha = +inf passes (y = 0 or a subnormal, p tiny);
+//  * a radial factor's centre (z = NaN) is not flat: flat_lane reports it per lane.
+// Every other lane -- and, in the walk, the whole wave when one colliding lane is not
+// trivial -- runs sigma_prime_from itself (tests/test_flat_sigma.py sweeps the floats).
+constexpr float kFlatAlphaC = 0.1678f;
+WOST_HD float flat_alpha_min(float inv_sb) {
+    const float a = fabsf(inv_sb);
+    if (!(a <= 0x1p64f)) return WOST_NAN;
+    const float b = kFlatAlphaC * a;
+    return b < 1e-8f ? 1e-8f : b;
+}
+// The z of this lane's whole-field saturated jet {v, z, z, z} is the zero (not the NaN of a
+// radial factor's centre): the walk's sigma' shortcut may take the lane.
+WOST_HD bool flat_lane(float z) { return z == 0.0f; }
+WOST_HD bool flat_sigma_trivial(bool flat, float alpha_v, float alpha_min) {
+    return flat && alpha_v >= alpha_min;
+}
+
 // ---------------------------------------------------------------------------
 // Screened Green's function norm (solvers/utils.py:29-44):
 //   G_norm(R) = (1/sigma_bar) (1 - 1/I0(R sqrt(sigma_bar)))

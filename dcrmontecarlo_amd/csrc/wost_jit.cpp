@@ -292,34 +292,49 @@ std::string sat_call(const DFactor& f) {
 
 constexpr int kVoteStatsFlag = 1 << 30;   // jet_body's xflags: option vote_stats (above exp_flags' bits)
 
+// The whole-field saturation predicate of a field (wost_device.h): the conjunction of its
+// factors' sat_* calls, "" when a factor has none, a coefficient is not finite or every
+// factor is an indicator. *radial: a radial factor is among them (its centre makes z NaN).
+std::string field_sat_predicate(const DField& fd, const DTerm* terms, const DFactor* factors, bool* radial) {
+    std::ostringstream s;
+    bool ok = fd.n_terms > 0;
+    *radial = false;
+    for (int t = 0; t < fd.n_terms && ok; ++t) {
+        const DTerm& tm = terms[fd.first_term + t];
+        ok = std::isfinite(tm.coef);
+        for (int k = 0; k < tm.nf && ok; ++k) {
+            const DFactor& f = factors[tm.first + k];
+            const std::string c = sat_call(f);
+            ok = !c.empty();
+            *radial |= f.kind == WOST_FK_SIGMOID_RADIAL;
+            if (ok && c != "true") s << (s.tellp() > 0 ? " & " : "") << c;
+        }
+    }
+    return ok ? s.str() : std::string();
+}
+
 // Same operation sequence as wost::field_jet. When every factor has a saturation
 // predicate and the coefficients are finite, a wave whose lanes are all saturated
 // returns {value, z, z, z} (wost_device.h, whole-field saturation): the value from
 // `value_fn` (the field's value body, the same bits as the jet's value there).
-std::string jet_body(const DField& fd, const DTerm* terms, const DFactor* factors, const char* value_fn, int xflags) {
+// flat_out: the body of the overload with `bool& flat`, which reports the lanes of that
+// return whose z is 0 (wost_device.h flat_lane: the walk's sigma' shortcut).
+std::string jet_body(const DField& fd, const DTerm* terms, const DFactor* factors, const char* value_fn, int xflags,
+                     bool flat_out = false) {
     std::ostringstream o;
+    if (flat_out) o << "        flat = false;\n";
     if (value_fn != nullptr && !(xflags & 512)) {
-        std::ostringstream s;
-        bool ok = fd.n_terms > 0, radial = false;
-        for (int t = 0; t < fd.n_terms && ok; ++t) {
-            const DTerm& tm = terms[fd.first_term + t];
-            ok = std::isfinite(tm.coef);
-            for (int k = 0; k < tm.nf && ok; ++k) {
-                const DFactor& f = factors[tm.first + k];
-                const std::string c = sat_call(f);
-                ok = !c.empty();
-                radial |= f.kind == WOST_FK_SIGMOID_RADIAL;
-                if (ok && c != "true") s << (s.tellp() > 0 ? " & " : "") << c;
-            }
-        }
-        if (ok && s.tellp() > 0) {
+        bool radial = false;
+        const std::string sat = field_sat_predicate(fd, terms, factors, &radial);
+        if (!sat.empty()) {
             o << "        {\n"
               << "            bool centre = false;\n"
-              << "            const bool sat = " << s.str() << ";\n"
+              << "            const bool sat = " << sat << ";\n"
               << ((xflags & kVoteStatsFlag) ? "            WOST_VOTE(12, !sat);\n" : "")
-              << "            if (WOST_SAT_ALL(sat)) {\n"
-              << "                const float z = " << (radial ? "centre ? __builtin_nanf(\"\") : 0.0f" : "0.0f")
+              << "            if (WOST_SAT_ALL(sat)) {\n";
+            o << "                const float z = " << (radial ? "centre ? __builtin_nanf(\"\") : 0.0f" : "0.0f")
               << ";\n"
+              << (flat_out ? "                flat = wost::flat_lane(z);\n" : "")
               << "                return wost::Jet{" << value_fn << "(x, y), z, z, z};\n"
               << "            }\n"
               << "        }\n";
@@ -751,6 +766,19 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
     if (opt.tree_share_min >= 1) o << "#define WOST_TREE_SHARE_MIN " << opt.tree_share_min << "\n";
     if (opt.tree_batch >= 1) o << "#define WOST_TREE_BATCH " << (opt.tree_batch >= 4 ? 4 : opt.tree_batch >= 2 ? 2 : 1) << "\n";
     const int nm = v.n_models >= 2 && prog.models != nullptr ? v.n_models : 1;   // NM (model batching)
+    // Options::flat_sigma_prime: a kernel whose sigma is the constant 0 and whose alpha jet has
+    // the whole-field saturated return skips sigma' on the wave-steps where every colliding
+    // lane's jet is that flat one (wost_device.h flat_alpha_min; one model, no wavenumbers)
+    bool flat_sp = false;
+    bool sigma_zero = true;   // absent, or constant terms that are all 0 (the library's default sigma)
+    for (int t = 0; fS.present && t < fS.n_terms; ++t)
+        sigma_zero = sigma_zero && terms[fS.first_term + t].nf == 0 && terms[fS.first_term + t].coef == 0.0f;
+    if (opt.flat_sigma_prime && delta && nm == 1 && v.n_wavenumbers < 1 && sigma_zero && fA.present &&
+        !(fA.flags & WOST_FIELD_DETACHED) && !(xf & 512)) {
+        bool radial = false;
+        flat_sp = !field_sat_predicate(fA, terms, factors, &radial).empty();
+    }
+    if (flat_sp) o << "#define WOST_FLAT_SIGMA_PRIME 1\n";
     o << "// generated by libwost (wost_jit.cpp): walk kernel, " << traits_name(t);
     if (nm >= 2) o << ", " << nm << " models";
     o << "\n"
@@ -790,8 +818,14 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
       << (fS.present ? value_body(fS, terms, factors) : "        return 0.0f;\n") << "    }\n";
     o << "    __device__ __forceinline__ float alpha(float x, float y) const {\n"
       << (fA.present ? value_body(fA, terms, factors) : "        return 1.0f;\n") << "    }\n";
-    o << "    __device__ __forceinline__ wost::Jet alpha_jet(float x, float y) const {\n"
-      << (fA.present ? jet_body(fA, terms, factors, (fA.flags & WOST_FIELD_DETACHED) ? nullptr : "alpha",
+    if (flat_sp)   // the walk's call: the jet, and which lanes took the flat return with z = 0
+        o << "    __device__ __forceinline__ wost::Jet alpha_jet(float x, float y, bool& flat) const {\n"
+          << jet_body(fA, terms, factors, "alpha", xf | (opt.vote_stats ? kVoteStatsFlag : 0), true) << "    }\n"
+          << "    __device__ __forceinline__ wost::Jet alpha_jet(float x, float y) const {\n"
+          << "        bool flat;\n        return alpha_jet(x, y, flat);\n    }\n";
+    else
+        o << "    __device__ __forceinline__ wost::Jet alpha_jet(float x, float y) const {\n"
+          << (fA.present ? jet_body(fA, terms, factors, (fA.flags & WOST_FIELD_DETACHED) ? nullptr : "alpha",
                                     xf | (opt.vote_stats ? kVoteStatsFlag : 0)) : "        return wost::jet_const(1.0f);\n") << "    }\n";
     o << "    __device__ __forceinline__ bool detached() const { return "
       << ((fA.flags & WOST_FIELD_DETACHED) ? "true" : "false") << "; }\n";

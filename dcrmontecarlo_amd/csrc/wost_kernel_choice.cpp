@@ -222,8 +222,11 @@ namespace {
 // then the charges' source count, sources NULL).
 int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
                        int32_t n_wavenumbers, int32_t n_charges, char* out, int64_t capacity, int64_t* length,
-                       const wost_model* models = nullptr, int32_t n_models = 0) {
+                       const wost_model* models = nullptr, int32_t n_models = 0, const char* const* opt_names = nullptr,
+                       const double* opt_values = nullptr, int32_t n_options = 0) {
     if (!pb || !length) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
+    if (n_options < 0 || (n_options > 0 && (!opt_names || !opt_values)))
+        return fail(WOST_ERR_INVALID_ARG, "need n_options >= 0 names and values");
     if (n_models < 0 || n_models > WOST_MAX_SOURCES || (n_models > 0 && !models))
         return fail(WOST_ERR_INVALID_ARG, "need 0..%d models", WOST_MAX_SOURCES);
     if (n_sources < 0 || n_sources > WOST_MAX_SOURCES || (n_charges == 0 && n_sources > 0 && !sources))
@@ -234,6 +237,8 @@ int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources,
     int rc = create_host(pb, &owner);
     if (rc != WOST_OK) return rc;
     wost_handle* h = owner.get();
+    for (int i = 0; i < n_options; ++i)   // wost_set_option, without a device
+        if ((rc = wost_set_option(h, opt_names[i], opt_values[i])) != WOST_OK) return rc;
     if (n_wavenumbers > 0 && !h->delta)
         return fail(WOST_ERR_UNSUPPORTED, "wavenumbers need delta tracking: give sigma or alpha (a constant alpha is enough)");
     h->n_wavenumbers = n_wavenumbers;
@@ -302,6 +307,11 @@ int wost_kernel_source_models(const wost_problem* pb, const wost_model* models, 
                               const wost_field* const* sources, int32_t n_sources, int32_t n_wavenumbers, char* out,
                               int64_t capacity, int64_t* length) {
     return kernel_source_impl(pb, sources, n_sources, n_wavenumbers, 0, out, capacity, length, models, n_models);
+}
+
+int wost_kernel_source_options(const wost_problem* pb, const char* const* names, const double* values,
+                               int32_t n_options, char* out, int64_t capacity, int64_t* length) {
+    return kernel_source_impl(pb, nullptr, 0, 0, 0, out, capacity, length, nullptr, 0, names, values, n_options);
 }
 
 int wost_kernel_source_sources(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,

@@ -41,6 +41,7 @@ const Spec kSpecs[] = {
     {"fused_scan", &Options::fused_scan, nullptr, 0, 1, true, false, nullptr},
     {"refill_min", &Options::refill_min, nullptr, -1, 64, true, false, "WOST_JIT_REFILL_MIN"},
     {"philox_ahead", &Options::philox_ahead, nullptr, -1, 3, true, false, "WOST_JIT_PHILOX_AHEAD"},
+    {"flat_sigma_prime", &Options::flat_sigma_prime, nullptr, 0, 1, true, false, nullptr},
     {"param_sources", &Options::param_sources, nullptr, 0, 1, true, false, nullptr},
     {"jit_process", &Options::jit_process, nullptr, 0, 1, false, false, nullptr},
     {"jit_race", &Options::jit_race, nullptr, 0, 1, false, false, nullptr},

@@ -53,6 +53,8 @@ struct Options {
     int fused_scan = 1;
     int refill_min = -1;            // idle lanes that trigger a refill (-1: WOST_REFILL_MIN)
     int philox_ahead = -1;          // Philox words one step ahead (-1: off)
+    int flat_sigma_prime = 1;       // sigma = 0 kernels skip sigma' where every colliding lane's alpha
+                                    // jet is the flat saturated one (wost_device.h flat_alpha_min)
     int param_sources = 0;          // multi-source kernels read the sources' parameters from the
                                     // program buffer (one compile per source structure; wost_jit.cpp)
     int jit_process = 1;            // compile in the helper process wost_jitc (the same code object;

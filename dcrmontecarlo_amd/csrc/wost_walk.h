@@ -874,6 +874,13 @@ __device__ __forceinline__ Hit intersect_polylines_tree_wave(const SegTree& t, f
 #ifndef WOST_WAVENUMBERS
 #define WOST_WAVENUMBERS 0
 #endif
+// WOST_FLAT_SIGMA_PRIME 1 (generated kernels whose sigma is the constant 0, option
+// flat_sigma_prime): the Fields policy also provides alpha_jet(x, y, bool& flat), and the
+// delta update skips sigma' where every colliding lane's weight is exactly 1
+// (wost_device.h flat_alpha_min). The other kernels compile none of it.
+#ifndef WOST_FLAT_SIGMA_PRIME
+#define WOST_FLAT_SIGMA_PRIME 0
+#endif
 // Walk pools (TREE kernels): see the exchange in walk_body. WOST_TREE_POOL 0 compiles
 // them out; WOST_POOL_MIN_PUSH: fewest mismatched walks a wave parks at once.
 #ifndef WOST_TREE_POOL
@@ -1053,6 +1060,10 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     const float sigma_bar = fld.sigma_bar();
     const float inv_sb = fld.inv_sigma_bar();
     const float sqrt_sb = fld.sqrt_sigma_bar();
+    // sigma' shortcut of the sigma = 0 kernels (wost_device.h flat_alpha_min): the generator
+    // defines WOST_FLAT_SIGMA_PRIME and gives alpha_jet the `flat` out-parameter
+    constexpr bool kFlatSigmaPrime = WOST_FLAT_SIGMA_PRIME && DELTA && NM == 1 && NK == 1 && !WOST_WAVENUMBERS;
+    const float flat_amin = kFlatSigmaPrime ? flat_alpha_min(inv_sb) : 0.0f;
 
     const int lane = threadIdx.x & 63;
     const uint64_t lanebit = 1ull << lane;
@@ -1492,6 +1503,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         float gnorm = 0.f;
         Jet aj{0.f, 0.f, 0.f, 0.f};
         Jet ajm[NM];                                                 // (NM > 1) every model's jet at y; ajm[0] = aj
+        bool aj_flat = false;                                        // (kFlatSigmaPrime) aj is {v, 0, 0, 0}
         WOST_PHASE("sample_and_clip");
         if (SRC) {                                                   // :242-258
             float rs;
@@ -1541,6 +1553,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 if constexpr (NM > 1) {
                     fld.alpha_jet_multi(yx, yy, ajm);
                     aj = ajm[0];
+                } else if constexpr (kFlatSigmaPrime) {
+                    aj = fld.alpha_jet(yx, yy, aj_flat);
                 } else {
                     aj = fld.alpha_jet(yx, yy);
                 }
@@ -1676,7 +1690,17 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             float sc[NW];
 #pragma unroll
             for (int j = 0; j < NW; ++j) sc[j] = 1.0f;
-            if (collide) {
+            // sigma = 0 kernels: a colliding lane whose jet is flat and whose alpha clears the
+            // bound has sc == 1.0f exactly (flat_alpha_min); the wave runs sigma' only when
+            // some colliding lane is not such a lane, and then for all of them as ever
+            bool sp_wave = true;
+            if constexpr (kFlatSigmaPrime) {
+                const bool full = collide && !flat_sigma_trivial(aj_flat, aj.v, flat_amin);
+                WOST_VOTE(13, full);
+                sp_wave = WOST_ANY(full);
+            }
+            if (sp_wave && collide) {
+                if constexpr (kFlatSigmaPrime) WOST_NO_SPECULATION();
                 float spv[NM];
                 if constexpr (NM > 1) {
                     float sg[NM];
@@ -1733,11 +1757,18 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             float sc[NW];
 #pragma unroll
             for (int j = 0; j < NW; ++j) sc[j] = 1.0f;
+            bool sp_wave = true;                                     // (see the FIX branch above)
+            if constexpr (kFlatSigmaPrime) {
+                const bool full = !accept && !flat_sigma_trivial(aj_flat, aj.v, flat_amin);
+                WOST_VOTE(13, full);
+                sp_wave = WOST_ANY(full);
+            }
 #if defined(WOST_ABL_NO_SIGMA_PRIME)
             if (false) {
 #else
-            if (!accept) {
+            if (sp_wave && !accept) {
 #endif
+                if constexpr (kFlatSigmaPrime) WOST_NO_SPECULATION();
                 float spv[NM];
                 if constexpr (NM > 1) {
                     float sg[NM];

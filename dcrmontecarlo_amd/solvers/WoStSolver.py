@@ -109,13 +109,16 @@ def _problem(dxy, nxy, g, f, sigma, alpha, compat, device, sigma_bar):
 
 def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoundary=None, source=None,
                   sigma=None, alpha=None, *, sigma_bar: float | None = None, compat: str = "reference",
-                  sources=None, n_wavenumbers: int = 0, models=None) -> str:
+                  sources=None, n_wavenumbers: int = 0, models=None, options: dict | None = None) -> str:
     """HIP source of the field-specialised walk kernel a WostSolver_2D with these
     arguments would compile (no device needed; wost_kernel_source). sources: the fields
     of a multi-source solve (solve_sources; wost_kernel_source_sources); n_wavenumbers: the
     wavenumbers of set_wavenumbers (wost_kernel_source_channels; 0: none); models: the
     (sigma, alpha) pairs of set_models (wost_kernel_source_models; None: that entry point is
-    not used, an empty list: it is, with no model)."""
+    not used, an empty list: it is, with no model); options: {name: value} of set_option
+    (wost_kernel_source_options; the plain single-source kernel only)."""
+    if options and (sources or n_wavenumbers or models is not None):
+        raise ValueError("options: only with the problem's own source, no wavenumbers and no models")
     dxy = np.asarray(_np(dirichletBoundary.points), dtype=np.float32).reshape(-1, 2)
     nxy = None if neumannBoundary is None else np.asarray(_np(neumannBoundary.points), dtype=np.float32).reshape(-1, 2)
     conv = _Converter(_bounds_of(dxy, nxy))
@@ -146,6 +149,11 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
         call = lambda buf, cap: _lib.lib.wost_kernel_source_models(ctypes.byref(prob), marr, len(models), arr,
                                                                     len(packed), int(n_wavenumbers), buf, cap,
                                                                     ctypes.byref(n))
+    if options:
+        names = (ctypes.c_char_p * len(options))(*[k.encode() for k in options])
+        values = (ctypes.c_double * len(options))(*[float(v) for v in options.values()])
+        call = lambda buf, cap: _lib.lib.wost_kernel_source_options(ctypes.byref(prob), names, values, len(options),
+                                                                     buf, cap, ctypes.byref(n))
     _lib.check(call(None, 0), "wost_kernel_source")
     buf = ctypes.create_string_buffer(n.value + 1)
     _lib.check(call(buf, n.value + 1), "wost_kernel_source")

@@ -586,7 +586,8 @@ int wost_set_segment_tree(wost_handle* h, int32_t min_segments, int32_t leaf_seg
  * default walk for walk. Names (dcrmontecarlo_amd/csrc/wost_options.h): tree_pool,
  * pool_near, pool_slots, pool_near_waves, pool_min_push, tree_lds, tree_lds_block,
  * tree_share, tree_share_min, tree_share_descent, tree_batch, tree_qmargin, jit_waves,
- * const_vertices, jit_slp, walk_block, fused_scan, refill_min, philox_ahead, param_sources, jit_process, jit_race,
+ * const_vertices, jit_slp, walk_block, fused_scan, refill_min, flat_sigma_prime, philox_ahead, param_sources,
+ * jit_process, jit_race,
  * chunk0,
  * chunk_min, chunk_max, adaptive_chunk, grid_blocks_per_cu, lds_pad_bytes.
  * WOST_ERR_INVALID_ARG for an unknown name or a value out of range; WOST_ERR_UNSUPPORTED
@@ -612,6 +613,11 @@ int wost_kernel_source(const wost_problem* problem, char* out, int64_t capacity,
  * default; option param_sources = 1 reads them from the program buffer instead). */
 int wost_kernel_source_sources(const wost_problem* problem, const wost_field* const* sources, int32_t n_sources,
                                char* out, int64_t capacity, int64_t* length);
+
+/* wost_kernel_source for a handle with n_options options set first (wost_set_option's names,
+ * values and refusals): the source such a handle would build. Host only. */
+int wost_kernel_source_options(const wost_problem* problem, const char* const* names, const double* values,
+                               int32_t n_options, char* out, int64_t capacity, int64_t* length);
 
 /* The same for n_wavenumbers wavenumbers on top (wost_set_wavenumbers; 0: none, as
  * wost_kernel_source_sources), so that a machine without a GPU can generate and compile the

@@ -22,7 +22,7 @@ SITES = ["walk-step (lanes stepping)", "sqrt_rn: x outside [2^-96, inf)", "norm_
          "fv_exp_quad_diag: exp needed", "fv_sigmoid_radial: unsaturated", "fj_exp_quad_diag: exp needed",
          "fj_sigmoid_radial: unsaturated", "sigma_prime_from: acp != ac", "poly_distance_const: redo",
          "ray test: tiny t", "unit_direction: !fast", "ray test: candidate body (IEEE division)",
-         "generated alpha_jet: not saturated"]
+         "generated alpha_jet: not saturated", "delta update: a colliding lane needs sigma'"]
 SIZES = {"dcr_dipole": ("C4", 48, 1_000_000), "variable_coefficients": ("C3", 256, 100_000)}
 
 
