@@ -28,13 +28,15 @@ WOST_COMM_SUM, WOST_COMM_MAX = 0, 1
 WOST_BLOCK_WALKS = 4096
 WOST_MAX_SOURCES = 16   # include/wost.h
 WOST_MAX_POINT_CHARGES = 32   # include/wost.h
+WOST_DTREE_MIN_SEGMENTS_DEFAULT = 128   # include/wost.h (wost_set_dirichlet_tree; measured)
+WOST_DTREE_LEAF_DEFAULT = 10
 WOST_TRIG = {"auto": 0, "exact": 1, "fast": 2}   # include/wost.h wost_trig
 WOST_SAMPLER_TABLE_N = 4097
 COMPAT = {"reference": 0, "fixed": 1}
 SLOT_BOUNDARY, SLOT_SOURCE = 0, 1
 GEOM_OPS = {"distance": 0, "isSilhouette": 1, "silhouetteDistance": 2, "rayIntersection": 3,
             "intersectPolylines": 4}
-WOST_GEOM_TREE = 256   # wost_geom_op flag: the query through the segment tree (ops 2 and 4)
+WOST_GEOM_TREE = 256   # wost_geom_op flag: the query through the segment tree (ops 0, 2 and 4)
 
 
 class WostFactor(ctypes.Structure):
@@ -176,6 +178,11 @@ def _load():
         "wost_set_trig": (c_int32, [H, c_int32]),
         "wost_set_fixed_step_check": (c_int32, [H, c_int32]),
         "wost_set_segment_tree": (c_int32, [H, c_int32, c_int32]),
+        "wost_set_dirichlet_tree": (c_int32, [H, c_int32, c_int32]),
+        "wost_dirichlet_tree_info": (c_int32, [H, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                               POINTER(c_int32)]),
+        "wost_kernel_source_dirichlet_tree": (c_int32, [POINTER(WostProblem), c_int32, c_int32, c_int32, c_int32,
+                                                        ctypes.c_char_p, c_int64, POINTER(c_int64)]),
         "wost_set_option": (c_int32, [H, c_char_p, c_double]),
         "wost_get_option": (c_int32, [H, c_char_p, POINTER(c_double)]),
         "wost_options_report": (c_int32, [H, ctypes.c_char_p, c_int64, POINTER(c_int64)]),

@@ -57,6 +57,7 @@ int create_host(const wost_problem* pb, HandlePtr* out) {
         (rc = convert_field(pb->alpha, h->fields[SLOT_ALPHA], "alpha")) != WOST_OK)
         return rc;
     h->compat = pb->compat;
+    h->dtree_usable = dirichlet_tree_usable(h->dverts.data(), (int)(h->dverts.size() / 2));
 #if defined(WOST_STUDY)
     // study builds only: the tools' A/B environment (the product library reads none of it;
     // wost_set_jit / wost_set_trig / wost_set_segment_tree / wost_set_option instead)
@@ -442,6 +443,27 @@ int wost_set_segment_tree(wost_handle* h, int32_t min_segments, int32_t leaf_seg
     return WOST_OK;
 }
 
+int wost_set_dirichlet_tree(wost_handle* h, int32_t min_segments, int32_t leaf_segments) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    if (leaf_segments < 0 || leaf_segments > 32) return fail(WOST_ERR_INVALID_ARG, "leaf_segments must be in [0, 32]");
+    h->dtree_min_segments = min_segments;
+    if (leaf_segments > 0 && leaf_segments != h->dtree_leaf) {
+        h->dtree_leaf = leaf_segments;
+        h->dtree_ready = false;
+    }
+    return WOST_OK;
+}
+
+int wost_dirichlet_tree_info(const wost_handle* h, int32_t* min_segments, int32_t* leaf_segments, int32_t* usable,
+                             int32_t* last_solve) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    if (min_segments) *min_segments = h->dtree_min_segments;
+    if (leaf_segments) *leaf_segments = h->dtree_leaf;
+    if (usable) *usable = h->dtree_usable ? 1 : 0;
+    if (last_solve) *last_solve = h->dtree_last ? 1 : 0;
+    return WOST_OK;
+}
+
 int wost_set_trig(wost_handle* h, int32_t mode) {
     if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
     if (mode != WOST_TRIG_AUTO && mode != WOST_TRIG_EXACT && mode != WOST_TRIG_FAST)
@@ -520,10 +542,14 @@ int wost_geometry_query(int32_t device, int32_t op, const wost_polyline* poly, c
     const bool tree = (op & WOST_GEOM_TREE) != 0;
     op &= ~WOST_GEOM_TREE;
     if (op < WOST_GEOM_DISTANCE || op > WOST_GEOM_INTERSECT_POLYLINES) return fail(WOST_ERR_INVALID_ARG, "unknown op %d", op);
-    if (tree && op != WOST_GEOM_SILHOUETTE_DISTANCE && op != WOST_GEOM_INTERSECT_POLYLINES)
-        return fail(WOST_ERR_INVALID_ARG, "the segment tree answers silhouetteDistance and intersectPolylines only");
+    if (tree && op != WOST_GEOM_DISTANCE && op != WOST_GEOM_SILHOUETTE_DISTANCE && op != WOST_GEOM_INTERSECT_POLYLINES)
+        return fail(WOST_ERR_INVALID_ARG,
+                    "the segment tree answers distance, silhouetteDistance and intersectPolylines only");
     const int nv = poly->n_vertices;
     if (tree && nv < 3) return fail(WOST_ERR_INVALID_ARG, "the segment tree needs >= 2 segments");
+    if (tree && op == WOST_GEOM_DISTANCE && !dirichlet_tree_usable(poly->xy, nv))
+        return fail(WOST_ERR_INVALID_ARG, "the distance through the segment tree needs segments of nonzero length and "
+                                          "finite coordinates up to 2^60 (wost_set_dirichlet_tree)");
     if ((op == WOST_GEOM_DISTANCE || op == WOST_GEOM_RAY_INTERSECTION || op == WOST_GEOM_INTERSECT_POLYLINES) && nv < 2)
         return fail(WOST_ERR_INVALID_ARG, "op %d needs a polyline with >= 2 vertices", op);
     if (n < 0 || (n > 0 && !points)) return fail(WOST_ERR_INVALID_ARG, "bad points");
@@ -537,7 +563,8 @@ int wost_geometry_query(int32_t device, int32_t op, const wost_polyline* poly, c
     if ((nf_out > 0 && !out_f) || (nm_out > 0 && !out_mask)) return fail(WOST_ERR_INVALID_ARG, "output buffer missing");
     if (n == 0) return WOST_OK;
     SegmentTreeHost th;
-    if (tree && !build_segment_tree(poly->xy, nv, WOST_TREE_LEAF_DEFAULT, &th) &&
+    const int leaf = op == WOST_GEOM_DISTANCE ? WOST_DTREE_LEAF_DEFAULT : WOST_TREE_LEAF_DEFAULT;
+    if (tree && !build_segment_tree(poly->xy, nv, leaf, &th) &&
         !build_segment_tree(poly->xy, nv, 32, &th))
         return fail(WOST_ERR_INVALID_ARG, "no segment tree for this polyline (degenerate or too long)");
     HIP_TRY(hipSetDevice(device));

@@ -1646,6 +1646,23 @@ struct SegTree {
         return rec[8 * k + i];
 #endif
     }
+    // the unstaged branches of vert / word under names of their own: those two switch on the
+    // staging macros of the kernel's NEUMANN tree, and a kernel that stages that tree also
+    // queries the Dirichlet tree (poly_distance_tree), of which nothing is staged
+    WOST_HD float2 gvert(int i) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return ((const __attribute__((address_space(1))) float2*)v)[i];
+#else
+        return v[i];
+#endif
+    }
+    WOST_HD float4 gword(int k, int i) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return ((const __attribute__((address_space(1))) float4*)rec)[8 * k + i];
+#else
+        return rec[8 * k + i];
+#endif
+    }
 };
 
 #ifndef WOST_CONE_MARGIN
@@ -1870,6 +1887,168 @@ WOST_HD float silhouette_distance_tree(const SegTree& t, float px, float py, flo
         live = resume();
     }
     return best == WOST_INF ? best : sqrt_rn(best);
+}
+
+// One child's lower bound for poly_distance_tree: the box part of
+// silhouette_child_keep_q (the same operations; the arc words are not read).
+WOST_HD float dirichlet_child_bound(float4 cu, float a, float b, float px, float py, float sl) {
+#pragma clang fp contract(off)
+    const float wx = px - cu.x, wy = py - cu.y;
+    const float pu = wx * cu.z + wy * cu.w, pn = wy * cu.z - wx * cu.w;
+    float gu = (fabsf(pu) - a) - sl, gn = (fabsf(pn) - b) - sl;
+    gu = gu > 0.0f ? gu : 0.0f;
+    gn = gn > 0.0f ? gn : 0.0f;
+    return a < 0.0f ? WOST_INF : (gu * gu + gn * gn) * 0.99999904632568359375f;   // 1 - 2^-20
+}
+
+// poly_distance (the Dirichlet distance of :208) over the segment tree of the Dirichlet
+// polyline: the minimum over the segments of poly_distance_with's d2 -- the same IEEE
+// division, clamps, lerp and ex*ex + ey*ey, contraction off -- and one sqrt_rn at the end,
+// visiting only the children whose box lower bound l does not exceed the best d2 so far.
+// The traversal is silhouette_distance_tree's: nearest child first, 4 pending bits per
+// level, re-test on resume, while-while leaf scans. Each segment belongs to one leaf
+// (the right neighbour's first segment, which a node's box also holds, is left to that
+// neighbour). Every `resume` clears the pending bits of the level it takes up before it
+// sets any of that level again and only ever sets bits of the level it descends from, and
+// a descent ends at a leaf after at most `depth` visits: pend reaches 0 and the search ends.
+//
+// The host offers the tree only for polylines that dirichlet_tree_usable accepts
+// (wost_tree.h): every segment has duu > 0 as computed here and every coordinate is at most
+// 2^60 in magnitude. With |px|, |py| <= 2^60 too, every quantity of a segment test is
+// finite (duv, duu <= 2^123, d2 <= 2^125), so no d2 is NaN and the scan's NaN bookkeeping
+// has nothing to record; any other query point (larger, infinite, NaN), where a product
+// can overflow and inf - inf give NaN at one segment and not at another, takes the full
+// scan -- the scan's bits by construction. (So the search itself never sees a NaN: neither
+// a NaN flag in the leaf scans nor a NaN lower bound has to be handled.)
+//
+// Exactness. The result is a minimum of values, so neither the visiting order nor ties
+// matter; what must hold is that for every segment of a child's range its COMPUTED d2 is
+// at least the child's l. Let M = |c|_1 + a + b of the child (>= every |coordinate| in its
+// box) and W = |p|_1 + M; the query's scale qw = 1.001 (|p|_1 + kmax) is >= W + a + b for
+// every child (SegmentTreeHost::kmax), and u = 2^-24.
+//  * The computed closest point is c' = fl(fl(fl(1 - t) a) + fl(t b)) per coordinate, t in
+//    [0, 1]: fl(1 - t) is within u/2, each product and the sum within u/2 relative, so c'
+//    lies within 2.5 u M (per coordinate; 3.6 u M in norm) of the point (1 - t) a + t b of
+//    the true segment, which lies in the box (convex, holds both end vertices; the host
+//    inflates it by 16 u (|c|_1 + a + b) beyond the vertices in the float frame the
+//    kernels read, which covers the rounding of the stored centre, extents and axis).
+//  * ex = fl(c'x - px), ey likewise, and d2 = fl(fl(ex ex) + fl(ey ey)) >= |c' - p|^2 (1 - 4u).
+//  * The bound's gaps: w = fl(p - c) within u/2 relative, pu and pn two products and a sum
+//    of magnitudes <= |w|_1, so within 2 u |w|_1 <= 2 u W absolutely, the stored axis is a
+//    unit vector to 1.5 u (a relative error of the frame's scale: <= 1.5 u W on a gap), and
+//    the subtractions of a (b) and sl round by u/2 of values <= W each: the computed gap
+//    before the slack exceeds the true distance from c' to the box along that axis by at
+//    most (3.6 + 2 + 1.5 + 1) u W < 8.1 u W. The slack sl = 2^-20 qw = 16 u qw is about twice
+//    that, so gu <= |e . u|, gn <= |e . n| for e = c' - p in exact arithmetic, hence
+//    gu^2 + gn^2 <= |c' - p|^2, computed with a relative error <= 3u.
+//  * l = fl((gu^2 + gn^2) (1 - 16u)) <= |c' - p|^2 (1 + 3u)(1 - 16u)(1 + u/2) < |c' - p|^2
+//    (1 - 4u) <= d2.
+// (Underflow: a positive gu exceeds sl >= 16 u kmax, and the host refuses polylines with
+// kmax < 2^-40 -- dirichlet_tree_usable -- so gu^2 >= 2^-120 is a normal number and so is
+// every d2 >= l that matters; a gap of 0 gives l = 0.) The Neumann queries' constants are
+// the same ones; nothing had to be enlarged for this query.
+WOST_HD float poly_distance_tree(const SegTree& t, float px, float py) {
+#pragma clang fp contract(off)
+    const int nseg = t.nv - 1;
+    if (!(fabsf(px) <= 0x1p60f && fabsf(py) <= 0x1p60f))   // also NaN: the scan (see above)
+        return poly_distance(t.v, t.nv, px, py);
+    float best = WOST_INF;
+    int d = 0, pos = 0;
+    uint32_t pend = 0u;
+    float plb0 = WOST_INF, plb1 = WOST_INF, plb2 = WOST_INF, plb3 = WOST_INF, plb4 = WOST_INF;
+    const float qsl = 9.5367431640625e-07f * (((fabsf(px) + fabsf(py)) + t.kmax) * 1.001f);   // 2^-20 qw
+    auto plb_get = [&](int l) {
+        float v = -WOST_INF;
+        v = l == 0 ? plb0 : v; v = l == 1 ? plb1 : v; v = l == 2 ? plb2 : v;
+        v = l == 3 ? plb3 : v; v = l == 4 ? plb4 : v;
+        return v;
+    };
+    auto plb_set = [&](int l, float x) {
+        plb0 = l == 0 ? x : plb0; plb1 = l == 1 ? x : plb1; plb2 = l == 2 ? x : plb2;
+        plb3 = l == 3 ? x : plb3; plb4 = l == 4 ? x : plb4;
+    };
+    // the children `cand` of node (lvl, at) whose bound does not exceed the best so far, the
+    // nearest of them in nj and the smallest bound of the others in nb2
+    auto visit = [&](int lvl, int at, uint32_t cand, int& nj, float& nb2) {
+        const int k = tree_level_offset(lvl) + at;
+        uint32_t kept = 0u;
+        float nb = WOST_INF;
+        nb2 = WOST_INF;
+        nj = 0;
+        WOST_TREE_COUNT(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!((cand >> j) & 1u)) continue;
+            const float4 cu = t.gword(k, 2 * j), ab = t.gword(k, 2 * j + 1);
+            const float lb = dirichlet_child_bound(cu, ab.x, ab.y, px, py, qsl);
+            if (lb > best || ab.x < 0.0f) continue;   // (beyond the best so far, or padding)
+            if (kept == 0u || lb < nb) { nb2 = nb; nb = lb; nj = j; }
+            else if (lb < nb2) nb2 = lb;
+            kept |= 1u << j;
+        }
+        return kept;
+    };
+    auto resume = [&]() {
+        while (pend != 0u) {
+            const int p = highest_bit(pend) >> 2;
+            const uint32_t m = (pend >> (4 * p)) & 15u;
+            pend &= ~(15u << (4 * p));
+            if (plb_get(p) > best) continue;   // every pending child of this level is pruned
+            const int anc = pos >> (2 * (d - p));
+            int nj;
+            float nb2;
+            const uint32_t kept = visit(p, anc, m, nj, nb2);
+            if (kept) {
+                pend |= (kept & ~(1u << nj)) << (4 * p);
+                plb_set(p, nb2);
+                pos = 4 * anc + nj;
+                d = p + 1;
+                return true;
+            }
+        }
+        return false;
+    };
+    bool live = nseg >= 1;
+    while (live) {
+        while (live && d < t.depth) {
+            int nj;
+            float nb2;
+            const uint32_t kept = visit(d, pos, 15u, nj, nb2);
+            if (kept) {
+                pend |= (kept & ~(1u << nj)) << (4 * d);
+                plb_set(d, nb2);
+                pos = 4 * pos + nj;
+                ++d;
+            } else {
+                live = resume();
+            }
+        }
+        if (!live) break;
+        WOST_TREE_COUNT(1);
+        const int s0 = pos * t.leaf;
+        const int s1 = s0 + t.leaf < nseg ? s0 + t.leaf : nseg;
+        if (s0 < s1) {
+            float2 a = t.gvert(s0);
+            for (int i = s0; i < s1; ++i) {   // poly_distance_with's segment test
+                const float2 b = t.gvert(i + 1);
+                const float ux = b.x - a.x, uy = b.y - a.y;
+                const float vx = px - a.x, vy = py - a.y;
+                const float duv = vx * ux + vy * uy;
+                const float duu = ux * ux + uy * uy;
+                float tt = duv / duu;
+                tt = tt < 0.f ? 0.f : tt;
+                tt = tt > 1.f ? 1.f : tt;
+                const float cx = (1.0f - tt) * a.x + tt * b.x;
+                const float cy = (1.0f - tt) * a.y + tt * b.y;
+                const float ex = cx - px, ey = cy - py;
+                const float d2 = ex * ex + ey * ey;
+                best = d2 < best ? d2 : best;
+                a = b;
+            }
+        }
+        live = resume();
+    }
+    return sqrt_rn(best);
 }
 
 // intersect_polylines over the tree: the same winner as the full scan -- the

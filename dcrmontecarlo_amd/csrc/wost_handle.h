@@ -224,6 +224,17 @@ struct wost_handle {
     bool tree_ready = false;
     wost::SegmentTreeHost tree;
     wost::DeviceBuffer<float> d_tree;
+    // Dirichlet segment tree (wost_set_dirichlet_tree): the field-specialised kernel's
+    // Dirichlet distance goes through it when the polyline admits it (dtree_usable, decided
+    // once at creation: wost_tree.h dirichlet_tree_usable), has at least dtree_min_segments
+    // segments (< 0: never) and is not compiled into the kernel
+    int dtree_min_segments = WOST_DTREE_MIN_SEGMENTS_DEFAULT;
+    int dtree_leaf = WOST_DTREE_LEAF_DEFAULT;
+    bool dtree_usable = false;
+    bool dtree_ready = false;
+    bool dtree_last = false;   // the last solve's walk kernel used it
+    wost::SegmentTreeHost dtree;
+    wost::DeviceBuffer<float> d_dtree;
 
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = {};
@@ -279,6 +290,14 @@ inline bool use_tree(const wost_handle* h) {
     return nseg >= 1 && h->tree_min_segments >= 0 && nseg >= h->tree_min_segments;
 }
 
+// Whether the handle's field-specialised kernels find the Dirichlet distance through the
+// Dirichlet tree (a polyline short enough to be compiled in keeps poly_distance_const).
+inline bool use_dtree(const wost_handle* h) {
+    const int nd = (int)(h->dverts.size() / 2);
+    return h->jit_enabled && h->dtree_usable && h->dtree_min_segments >= 0 && nd - 1 >= h->dtree_min_segments &&
+           !jit_const_dirichlet(h->opt, nd);
+}
+
 // The traits of the handle's walks with a source term or not (delta tracking needs one:
 // check_request refuses the solve without).
 inline WalkTraits walk_traits(const wost_handle* h, bool src) {
@@ -293,6 +312,7 @@ void sampler_nodes_prefetch(int kind, double sigma_bar);
 const std::vector<float>& fixed_screened_table();
 int ensure_table(wost_handle* h);
 int ensure_tree(wost_handle* h);
+int ensure_dtree(wost_handle* h);
 int upload_program(wost_handle* h);
 int upload_charges(wost_handle* h);
 
@@ -305,6 +325,7 @@ constexpr int kTreeLdsDefaultLevel = 2;
 struct KernelShape {
     int block = kWalkBlock, tree_verts = 0, tree_level = kTreeLdsDefaultLevel, tree_lds = 0;
     bool gpoly = false;
+    bool dtree = false;   // the Dirichlet distance through the Dirichlet tree (no Dirichlet vertex staged)
     // the staging level compiled into the kernel (tree_lds_records)
     int stage() const { return tree_lds > 0 ? (tree_verts > 0 ? 2 : 1) : 0; }
 };

@@ -779,12 +779,19 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
         flat_sp = !field_sat_predicate(fA, terms, factors, &radial).empty();
     }
     if (flat_sp) o << "#define WOST_FLAT_SIGMA_PRIME 1\n";
+    // the Dirichlet distance through the Dirichlet polyline's segment tree (KernelVariant::
+    // dirichlet_tree; never for a compiled-in polyline)
+    const bool dtree = v.dirichlet_tree && !jit_const_dirichlet(opt, nd);
+    if (dtree) o << "#define WOST_DIRICHLET_TREE 1\n";
     o << "// generated by libwost (wost_jit.cpp): walk kernel, " << traits_name(t);
     if (nm >= 2) o << ", " << nm << " models";
+    if (dtree) o << ", dirichlet tree";
     o << "\n"
       << "#include \"wost_walk.h\"\n\nnamespace {\nstruct GenFields {\n"
       << "    const float* grid;   // tabulated field values (WOST_FK_GRID) in the program buffer\n"
-      << "    const char* pb;      // the program buffer (multi-source kernels read the sources' parameters)\n"
+      << "    const char* pb;      // the program buffer (multi-source kernels read the sources' parameters)\n";
+    if (dtree) o << "    const wost::WalkArgs* wa;   // the kernel's arguments (the Dirichlet tree's; null elsewhere)\n";
+    o
       << "    __device__ __forceinline__ static float pv(const char* p, unsigned off) {\n"
       << "        return *(const __attribute__((address_space(4))) float*)(p + off);\n    }\n";
     o << "    __device__ __forceinline__ bool has_g() const { return " << (fG.present ? "true" : "false") << "; }\n";
@@ -907,6 +914,8 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
               << "        return wost::poly_distance_const(v, rcp, " << nd << ", x, y);\n";
         else
             o << "        return wost::poly_distance(v, " << nd << ", x, y);\n";
+    } else if (dtree) {
+        o << "        return wost::poly_distance_tree(wost::dirichlet_seg_tree(*wa), x, y);\n";
     } else {
         o << "        return wost::poly_distance(sD, nd, x, y);\n";
     }
@@ -972,7 +981,7 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
       << "wost_walk_jit(const wost::WalkArgs A) {\n"
       << "    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];\n"
       << "    const GenFields fld{reinterpret_cast<const float*>(A.prog + "
-      << program_grid_offset(hdr.n_terms_total, hdr.n_factors_total) << "ull), A.prog};\n"
+      << program_grid_offset(hdr.n_terms_total, hdr.n_factors_total) << "ull), A.prog" << (dtree ? ", &A" : "") << "};\n"
       << "    wost::walk_body<" << (neu ? "true" : "false") << ", " << (src ? "true" : "false") << ", "
       << (delta ? "true" : "false") << ", " << (tree ? "true" : "false") << ", " << (v.record ? "true" : "false")
       << ", " << v.n_sources << ", " << (t.fix ? "true" : "false") << ", "
@@ -987,7 +996,8 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
         o << "extern \"C\" __global__ void __launch_bounds__(256)\n"
           << "wost_point_alpha_jit(const char* prog, const float2* pts, long long n, float* out) {\n"
           << "    const GenFields fld{reinterpret_cast<const float*>(prog + "
-          << program_grid_offset(hdr.n_terms_total, hdr.n_factors_total) << "ull), prog};\n"
+          << program_grid_offset(hdr.n_terms_total, hdr.n_factors_total) << "ull), prog" << (dtree ? ", nullptr" : "")
+          << "};\n"
           << (nm >= 2 ? "    wost::point_alpha_multi_body<" + std::to_string(nm) + ">(pts, (int64_t)n, out, fld);\n}\n"
                       : std::string("    wost::point_alpha_body(pts, (int64_t)n, out, fld);\n}\n"));
     return o.str();

@@ -100,7 +100,8 @@ size_t lds_of(const wost_handle* h, const WalkTraits& t, const KernelChoice& kc)
     // option lds_pad_bytes (occupancy studies): extra bytes of LDS per workgroup
     return walk_lds_bytes({.traits = t, .nd = nd_, .nn = (int)(h->nverts.size() / 2), .tree_lds = kc.shape.tree_lds,
                            .tree_verts = kc.shape.tree_verts, .const_d = jit && jit_const_dirichlet(h->opt, nd_),
-                           .global_polylines = jit && kc.shape.gpoly, .block = kc.shape.block}) +
+                           .global_polylines = jit && kc.shape.gpoly, .block = kc.shape.block,
+                           .dirichlet_tree = jit && kc.shape.dtree}) +
            (size_t)h->opt.lds_pad_bytes;
 }
 
@@ -134,7 +135,7 @@ KernelVariant kernel_variant(const wost_handle* h, const WalkTraits& t, const Ke
                          .n_wavenumbers = t.delta ? h->n_wavenumbers : 0,   // (0: the kernel without the k2 read)
                          .n_charges = (int)h->charges.size(), .n_models = t.delta ? h->n_models : 0,
                          .block = ks.block, .global_polylines = ks.gpoly,
-                         .tree_stage = ks.stage(), .exact_trig = exact_trig_of(h)};
+                         .tree_stage = ks.stage(), .exact_trig = exact_trig_of(h), .dirichlet_tree = ks.dtree};
 }
 
 int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* ks) {
@@ -149,7 +150,11 @@ int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* k
     // polylines whose LDS copy would cost the walk kernel its occupancy are read from
     // global memory instead (field-specialised kernels; the precompiled ones stage them)
     // (the staged tree records have their own budget, kTreeLdsMaxBytes)
+    // the Dirichlet tree (field-specialised kernels): no Dirichlet vertex is staged, so a long
+    // Dirichlet polyline no longer counts against the budget below
+    ks->dtree = use_dtree(h);
     WalkLds lds{.traits = t, .nd = nd_, .nn = nn_, .const_d = jit_const_dirichlet(O, nd_)};
+    lds.dirichlet_tree = ks->dtree;
     ks->gpoly = h->jit_enabled && walk_lds_bytes(lds) > kGlobalPolylineLdsBytes;
     // the brute-force scan of a long Neumann polyline (neumann_scan_both) reads every vertex
     // at every step: staged in LDS with one 1024-thread workgroup per CU when it fits (a
@@ -188,6 +193,7 @@ int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, i
                             h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
             ks.block = kWalkBlock;
             ks.tree_lds = ks.tree_verts = 0;
+            ks.dtree = false;   // (the precompiled kernels scan the Dirichlet polyline)
         }
         kc->lds = lds_of(h, t, *kc);
         kc->blocks_per_cu = 0;
@@ -223,7 +229,7 @@ namespace {
 int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
                        int32_t n_wavenumbers, int32_t n_charges, char* out, int64_t capacity, int64_t* length,
                        const wost_model* models = nullptr, int32_t n_models = 0, const char* const* opt_names = nullptr,
-                       const double* opt_values = nullptr, int32_t n_options = 0) {
+                       const double* opt_values = nullptr, int32_t n_options = 0, const int32_t* dtree = nullptr) {
     if (!pb || !length) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
     if (n_options < 0 || (n_options > 0 && (!opt_names || !opt_values)))
         return fail(WOST_ERR_INVALID_ARG, "need n_options >= 0 names and values");
@@ -237,6 +243,7 @@ int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources,
     int rc = create_host(pb, &owner);
     if (rc != WOST_OK) return rc;
     wost_handle* h = owner.get();
+    if (dtree && (rc = wost_set_dirichlet_tree(h, dtree[0], dtree[1])) != WOST_OK) return rc;
     for (int i = 0; i < n_options; ++i)   // wost_set_option, without a device
         if ((rc = wost_set_option(h, opt_names[i], opt_values[i])) != WOST_OK) return rc;
     if (n_wavenumbers > 0 && !h->delta)
@@ -269,7 +276,9 @@ int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources,
     // host's atan2f (the kernels use the device's bits; this source is for offline study)
     const std::vector<float> phi = segment_angles(h->nverts);
     // the first solve's kernel without a device: 256 threads, nothing of the tree staged
-    KernelVariant v = kernel_variant(h, t, KernelShape{}, false, ns);
+    KernelShape ks0;
+    ks0.dtree = use_dtree(h);
+    KernelVariant v = kernel_variant(h, t, ks0, false, ns);
     // study builds: offline study of the tree kernels' LDS staging (tools/jit_isa.py --stage):
     // the source of staging level WOST_KERNEL_SOURCE_STAGE (2: records and vertices, 1:
     // records, with the tree_lds_block workgroup) instead
@@ -312,6 +321,15 @@ int wost_kernel_source_models(const wost_problem* pb, const wost_model* models, 
 int wost_kernel_source_options(const wost_problem* pb, const char* const* names, const double* values,
                                int32_t n_options, char* out, int64_t capacity, int64_t* length) {
     return kernel_source_impl(pb, nullptr, 0, 0, 0, out, capacity, length, nullptr, 0, names, values, n_options);
+}
+
+int wost_kernel_source_dirichlet_tree(const wost_problem* pb, int32_t min_segments, int32_t leaf_segments,
+                                      int32_t n_charges, int32_t n_sources, char* out, int64_t capacity,
+                                      int64_t* length) {
+    if (n_charges < 0) return fail(WOST_ERR_INVALID_ARG, "need n_charges >= 0");
+    const int32_t dtree[2] = {min_segments, leaf_segments};
+    return kernel_source_impl(pb, nullptr, n_charges > 0 ? n_sources : 0, 0, n_charges, out, capacity, length, nullptr, 0,
+                              nullptr, nullptr, 0, dtree);
 }
 
 int wost_kernel_source_sources(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,

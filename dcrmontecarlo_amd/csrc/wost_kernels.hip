@@ -432,14 +432,28 @@ wost_geometry_tree_kernel(int op, SegTree t, const float2* __restrict__ pts, con
     }
 }
 
+// op 0 through the Dirichlet tree (poly_distance_tree), one query per lane:
+// wost_geometry_query(WOST_GEOM_DISTANCE | WOST_GEOM_TREE).
+__global__ void __launch_bounds__(256)
+wost_geometry_dtree_kernel(SegTree t, const float2* __restrict__ pts, int64_t n, float* __restrict__ out_f) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float2 p = pts[i];
+    out_f[i] = poly_distance_tree(t, p.x, p.y);
+}
+
 hipError_t launch_geometry_tree_query(int op, const float2* verts, int nv, const float4* rec, int first_leaf,
                                       int depth, int leaf, float tol, float kmax, const float2* pts,
                                       const float2* dirs, const float* radii, int64_t n, float* out_f,
                                       hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    if (op != WOST_GEOM_SILHOUETTE_DISTANCE && op != WOST_GEOM_INTERSECT_POLYLINES) return hipErrorInvalidValue;
     SegTree t{rec, verts, nv, first_leaf, depth, leaf, tol, kmax};
     const int64_t grid = (n + 255) / 256;
+    if (op == WOST_GEOM_DISTANCE) {
+        wost_geometry_dtree_kernel<<<(unsigned)grid, 256, 0, s>>>(t, pts, n, out_f);
+        return hipGetLastError();
+    }
+    if (op != WOST_GEOM_SILHOUETTE_DISTANCE && op != WOST_GEOM_INTERSECT_POLYLINES) return hipErrorInvalidValue;
     wost_geometry_tree_kernel<<<(unsigned)grid, 256, 0, s>>>(op, t, pts, dirs, radii, n, out_f);
     return hipGetLastError();
 }

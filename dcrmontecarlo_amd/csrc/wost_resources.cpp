@@ -154,6 +154,22 @@ int ensure_tree(wost_handle* h) {
     return WOST_OK;
 }
 
+// The Dirichlet tree of a handle whose polyline admits it (use_dtree), built and uploaded on
+// first use; the same fallback as ensure_tree when the builder refuses the leaf size.
+int ensure_dtree(wost_handle* h) {
+    if (h->dtree_ready) return WOST_OK;
+    const int nv = (int)(h->dverts.size() / 2);
+    if (!build_segment_tree(h->dverts.data(), nv, h->dtree_leaf, &h->dtree) &&
+        !build_segment_tree(h->dverts.data(), nv, 32, &h->dtree))
+        return fail(WOST_ERR_UNSUPPORTED, "cannot build the Dirichlet segment tree of %d segments (at most %d levels "
+                    "of 32-segment leaves)", nv - 1, kTreeMaxDepth);
+    HIP_TRY(h->d_dtree.reserve(std::max<size_t>(h->dtree.rec.size(), 16)));
+    if (!h->dtree.rec.empty())
+        HIP_TRY(hipMemcpy(h->d_dtree, h->dtree.rec.data(), sizeof(float) * h->dtree.rec.size(), hipMemcpyHostToDevice));
+    h->dtree_ready = true;
+    return WOST_OK;
+}
+
 // The device image of the handle's charges (WalkArgs::charges), alpha left at 1.
 int upload_charges(wost_handle* h) {
     std::vector<float> w((size_t)kChargeWords, 0.0f);

@@ -178,6 +178,14 @@ WalkArgs fill_walk_args(const wost_handle* h, const SolveRequest& rq, const Walk
         a.tree_lds_verts = kc.shape.tree_verts;
         a.tree_depth = h->tree.depth;
     }
+    if (kc.jfn && kc.shape.dtree) {   // (ensure_dtree has run: solve_impl)
+        const float* const rec = h->d_dtree;
+        a.dtree = reinterpret_cast<const float4*>(rec);
+        a.dtree_first_leaf = h->dtree.first_leaf;
+        a.dtree_depth = h->dtree.depth;
+        a.dtree_leaf = h->dtree.leaf;
+        a.dtree_kmax = h->dtree.kmax;
+    }
     return a;
 }
 
@@ -378,6 +386,7 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
     if ((rc = upload_program(h)) != WOST_OK) return rc;
     if (h->has_source() && (rc = ensure_table(h)) != WOST_OK) return rc;
     if (t.tree && (rc = ensure_tree(h)) != WOST_OK) return rc;
+    if (use_dtree(h) && (rc = ensure_dtree(h)) != WOST_OK) return rc;
     if (out.records && !h->charges.empty())
         return fail(WOST_ERR_UNSUPPORTED, "wost_solve_history does not record point sources (a step scores every "
                                           "charge in its ball: there is no sample point)");
@@ -540,5 +549,6 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
     h->timing.jit_ms = kc.jit_ms;
     h->timing.jit = kc.jfn ? 1 : 0;
     h->timing.tree = t.tree ? 1 : 0;
+    h->dtree_last = kc.jfn != nullptr && kc.shape.dtree;
     return WOST_OK;
 }

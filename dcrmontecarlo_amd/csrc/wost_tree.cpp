@@ -133,4 +133,22 @@ bool build_segment_tree(const float* xy, int nv, int leaf, SegmentTreeHost* out)
     return true;
 }
 
+bool dirichlet_tree_usable(const float* xy, int nv) {
+    if (nv < 2) return false;
+    float cmax = 0.f;
+    for (int i = 0; i < 2 * nv; ++i) {
+        if (!(std::fabs(xy[i]) <= 0x1p60f)) return false;   // (also NaN)
+        cmax = std::max(cmax, std::fabs(xy[i]));
+    }
+    if (!(cmax >= 0x1p-40f)) return false;
+    for (int i = 0; i + 1 < nv; ++i) {
+        // the squared length as the kernels form it: float operations, no contraction
+        volatile float ux = xy[2 * i + 2] - xy[2 * i], uy = xy[2 * i + 3] - xy[2 * i + 1];
+        volatile float xx = ux * ux, yy = uy * uy;
+        volatile float duu = xx + yy;
+        if (!(duu > 0.0f)) return false;
+    }
+    return true;
+}
+
 }  // namespace wost

@@ -34,4 +34,13 @@ struct SegmentTreeHost {
 // or a tree deeper than kTreeMaxDepth.
 bool build_segment_tree(const float* xy, int nv, int leaf, SegmentTreeHost* out);
 
+// Whether the Dirichlet distance of the polyline xy[2*nv] may go through a segment tree
+// (wost_device.h poly_distance_tree) and still return the full scan's bits: every segment
+// has a squared length > 0 as the kernels compute it (a zero-length segment makes the scan
+// return NaN wherever the query point is, and the tree cannot promise to visit it), every
+// coordinate is finite and at most 2^60 in magnitude (poly_distance_const's bound: no
+// overflow in a segment test), and the largest is at least 2^-40 (it bounds the tree's kmax
+// below: the lower bounds' squares stay normal numbers). At least one segment.
+bool dirichlet_tree_usable(const float* xy, int nv);
+
 }  // namespace wost

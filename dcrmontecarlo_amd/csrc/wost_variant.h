@@ -47,13 +47,16 @@ struct KernelVariant {
     int tree_stage = 0;              // tree kernels: 0 = the tree through L1/L2, 1 = its records in LDS
                                      // (WOST_TREE_STAGED), 2 = and the Neumann vertices (WOST_TREE_VSTAGED)
     bool exact_trig = true;          // wost_set_trig: correctly rounded directions
+    bool dirichlet_tree = false;     // the Dirichlet distance through the Dirichlet polyline's segment tree
+                                     // (poly_distance_tree; records and vertices through L1/L2, nothing staged)
 };
 
 inline bool operator==(const KernelVariant& a, const KernelVariant& b) {
     return a.traits == b.traits && a.record == b.record && a.n_sources == b.n_sources &&
            a.n_wavenumbers == b.n_wavenumbers && a.n_charges == b.n_charges && a.n_models == b.n_models &&
            a.block == b.block &&
-           a.global_polylines == b.global_polylines && a.tree_stage == b.tree_stage && a.exact_trig == b.exact_trig;
+           a.global_polylines == b.global_polylines && a.tree_stage == b.tree_stage && a.exact_trig == b.exact_trig &&
+           a.dirichlet_tree == b.dirichlet_tree;
 }
 
 }  // namespace wost

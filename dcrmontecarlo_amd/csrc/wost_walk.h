@@ -113,7 +113,21 @@ struct WalkArgs {
     // ... and boundary_code (wost_device.h) of each query point: a walk that starts on the
     // Neumann polyline starts as a walk that has just hit it there (PC > 0 kernels only)
     const int32_t* point_code;
+    // Dirichlet segment tree (wost_set_dirichlet_tree; read only by kernels built with
+    // WOST_DIRICHLET_TREE, through GenFields::dirichlet_distance): its records and the
+    // scalars of SegTree; null / 0 otherwise
+    const float4* dtree;
+    int32_t dtree_first_leaf;
+    int32_t dtree_depth;
+    int32_t dtree_leaf;
+    float dtree_kmax;
 };
+
+// The Dirichlet polyline's tree as poly_distance_tree reads it (records and vertices through
+// global loads; the line-test tolerance is the ray query's and unused).
+__device__ __forceinline__ SegTree dirichlet_seg_tree(const WalkArgs& A) {
+    return SegTree{A.dtree, A.dverts, A.nd, A.dtree_first_leaf, A.dtree_depth, A.dtree_leaf, 0.0f, A.dtree_kmax};
+}
 
 // Offsets of the per-charge arrays in WalkArgs::charges: position (x, y interleaved),
 // strength, alpha at the charge (delta tracking: point_alpha_body's bits), and as ints the
@@ -305,6 +319,7 @@ struct WalkLds {
     bool const_d = false;            // the Dirichlet polyline is compiled in (field-specialised kernels)
     bool global_polylines = false;   // nothing of the polylines is staged (wost_walk.h GL)
     int block = kWalkBlock;          // threads per workgroup
+    bool dirichlet_tree = false;     // the Dirichlet distance through its tree: no Dirichlet vertex staged
 };
 WOST_HD size_t walk_lds_bytes(const WalkLds& k) {
     const WalkTraits& t = k.traits;
@@ -312,7 +327,7 @@ WOST_HD size_t walk_lds_bytes(const WalkLds& k) {
     if (t.src) b += t.delta ? sizeof(float4) * (size_t)kGnormCells : 16;
     if (t.src) b += sizeof(float) * (size_t)kSamplerTailFloats;
     b = align16(b);
-    if (!k.const_d && !k.global_polylines) b += align16(sizeof(float2) * (size_t)k.nd);
+    if (!k.const_d && !k.global_polylines && !k.dirichlet_tree) b += align16(sizeof(float2) * (size_t)k.nd);
     if (t.neu && !t.tree && !k.global_polylines)
         b += align16(sizeof(float2) * (size_t)k.nn) + align16(sizeof(float) * (size_t)(k.nn > 1 ? k.nn - 1 : 0));
     if (t.tree)
@@ -881,6 +896,13 @@ __device__ __forceinline__ Hit intersect_polylines_tree_wave(const SegTree& t, f
 #ifndef WOST_FLAT_SIGMA_PRIME
 #define WOST_FLAT_SIGMA_PRIME 0
 #endif
+// WOST_DIRICHLET_TREE 1 (generated kernels of a handle whose Dirichlet distance goes through
+// the Dirichlet polyline's segment tree, wost_set_dirichlet_tree): the Fields policy holds
+// the kernel's arguments and its dirichlet_distance calls poly_distance_tree; walk_body
+// stages no Dirichlet vertex. The other kernels compile none of it.
+#ifndef WOST_DIRICHLET_TREE
+#define WOST_DIRICHLET_TREE 0
+#endif
 // Walk pools (TREE kernels): see the exchange in walk_body. WOST_TREE_POOL 0 compiles
 // them out; WOST_POOL_MIN_PUSH: fewest mismatched walks a wave parks at once.
 #ifndef WOST_TREE_POOL
@@ -1003,7 +1025,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                   "point sources need compat=\"fixed\", a source mode, no recorder, at most WOST_MAX_POINT_CHARGES charges");
     constexpr int NW = NM * NK;   // weights: wc = m * NK + j
     constexpr int NC = NW * NS;   // channels: c = (m * NK + j) * NS + s
-    constexpr bool kStageD = !F::kConstDirichlet && !GL;
+    // (a Dirichlet-tree kernel reads the vertices it needs through global loads)
+    constexpr bool kStageD = !F::kConstDirichlet && !GL && !WOST_DIRICHLET_TREE;
     // the Neumann polyline is staged also when compiled in (FIX scans sN itself; a few
     // hundred bytes otherwise)
     constexpr bool kStageN = NEU && !TREE && !GL;
@@ -1037,7 +1060,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         for (int i = threadIdx.x; i < A.nn - 1; i += blockDim.x) sPhi[i] = A.seg_phi[i];
     }
     // the polylines the queries read: the LDS copies, or (GL) global memory
-    const float2* const dP = GL ? A.dverts : sD;
+    const float2* const dP = (GL || WOST_DIRICHLET_TREE) ? A.dverts : sD;
     const float2* const nP = GL ? A.nverts : sN;
     const float* const phiP = GL ? A.seg_phi : sPhi;
     const SegTree tree{A.tree, A.nverts, A.nn, A.tree_first_leaf, A.tree_depth, A.tree_leaf, A.tree_tol, A.tree_kmax,

@@ -80,9 +80,11 @@ class PolyLinesSimple(PolyLines):
         return (out_f if out_m is None else out_m.astype(bool)), single
 
     # ---- reference API (PolylinesSimple.py:214-307) -------------------
-    def distance(self, point):
-        """Distance to the polyline (distance_to_polyline_jit, :25-49)."""
-        v, single = self._query("distance", point)
+    def distance(self, point, *, tree: bool = False):
+        """Distance to the polyline (distance_to_polyline_jit, :25-49). ``tree``: answered by
+        the walk kernels' Dirichlet segment tree (same bits as the scan; ValueError for a
+        polyline with a zero-length segment or a non-finite coordinate)."""
+        v, single = self._query("distance", point, tree=tree)
         if single:
             return _scalar(v[0]) if _is_torch(point) else np.float32(v[0])
         return _out(v, point)

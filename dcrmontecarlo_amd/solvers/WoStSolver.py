@@ -109,16 +109,22 @@ def _problem(dxy, nxy, g, f, sigma, alpha, compat, device, sigma_bar):
 
 def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoundary=None, source=None,
                   sigma=None, alpha=None, *, sigma_bar: float | None = None, compat: str = "reference",
-                  sources=None, n_wavenumbers: int = 0, models=None, options: dict | None = None) -> str:
+                  sources=None, n_wavenumbers: int = 0, models=None, options: dict | None = None,
+                  dirichlet_tree: int | None = None, dirichlet_tree_leaf: int = 0) -> str:
     """HIP source of the field-specialised walk kernel a WostSolver_2D with these
     arguments would compile (no device needed; wost_kernel_source). sources: the fields
     of a multi-source solve (solve_sources; wost_kernel_source_sources); n_wavenumbers: the
     wavenumbers of set_wavenumbers (wost_kernel_source_channels; 0: none); models: the
     (sigma, alpha) pairs of set_models (wost_kernel_source_models; None: that entry point is
     not used, an empty list: it is, with no model); options: {name: value} of set_option
-    (wost_kernel_source_options; the plain single-source kernel only)."""
+    (wost_kernel_source_options; the plain single-source kernel only); dirichlet_tree: the
+    min_segments of set_dirichlet_tree called first (0 forces the Dirichlet tree, -1 forbids
+    it, None: the default threshold; wost_kernel_source_dirichlet_tree, the plain
+    single-source kernel only), dirichlet_tree_leaf its leaf_segments."""
     if options and (sources or n_wavenumbers or models is not None):
         raise ValueError("options: only with the problem's own source, no wavenumbers and no models")
+    if dirichlet_tree is not None and (options or sources or n_wavenumbers or models is not None):
+        raise ValueError("dirichlet_tree: only with the problem's own source, no wavenumbers, models or options")
     dxy = np.asarray(_np(dirichletBoundary.points), dtype=np.float32).reshape(-1, 2)
     nxy = None if neumannBoundary is None else np.asarray(_np(neumannBoundary.points), dtype=np.float32).reshape(-1, 2)
     conv = _Converter(_bounds_of(dxy, nxy))
@@ -154,6 +160,9 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
         values = (ctypes.c_double * len(options))(*[float(v) for v in options.values()])
         call = lambda buf, cap: _lib.lib.wost_kernel_source_options(ctypes.byref(prob), names, values, len(options),
                                                                      buf, cap, ctypes.byref(n))
+    if dirichlet_tree is not None:
+        call = lambda buf, cap: _lib.lib.wost_kernel_source_dirichlet_tree(
+            ctypes.byref(prob), int(dirichlet_tree), int(dirichlet_tree_leaf), 0, 0, buf, cap, ctypes.byref(n))
     _lib.check(call(None, 0), "wost_kernel_source")
     buf = ctypes.create_string_buffer(n.value + 1)
     _lib.check(call(buf, n.value + 1), "wost_kernel_source")
@@ -162,10 +171,12 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
 
 def kernel_source_points(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoundary=None, sigma=None,
                          alpha=None, *, n_charges: int, n_sources: int = 1, n_wavenumbers: int = 0,
-                         sigma_bar: float | None = None, compat: str = "fixed") -> str:
+                         sigma_bar: float | None = None, compat: str = "fixed",
+                         dirichlet_tree: int | None = None) -> str:
     """HIP source of the walk kernel of a solver with ``n_charges`` point charges in
     ``n_sources`` source channels (set_point_sources; wost_kernel_source_points, no device
-    needed). It depends on the counts only: positions and strengths are run-time data."""
+    needed). It depends on the counts only: positions and strengths are run-time data.
+    dirichlet_tree: as kernel_source's (no wavenumbers then)."""
     dxy = np.asarray(_np(dirichletBoundary.points), dtype=np.float32).reshape(-1, 2)
     nxy = None if neumannBoundary is None else np.asarray(_np(neumannBoundary.points), dtype=np.float32).reshape(-1, 2)
     conv = _Converter(_bounds_of(dxy, nxy))
@@ -180,6 +191,11 @@ def kernel_source_points(dirichletBoundary, dirichletBoundaryFunction=None, neum
     n = ctypes.c_int64(0)
     call = lambda buf, cap: _lib.lib.wost_kernel_source_points(ctypes.byref(prob), int(n_charges), int(n_sources),
                                                                 int(n_wavenumbers), buf, cap, ctypes.byref(n))
+    if dirichlet_tree is not None:
+        if n_wavenumbers:
+            raise ValueError("dirichlet_tree: not together with wavenumbers")
+        call = lambda buf, cap: _lib.lib.wost_kernel_source_dirichlet_tree(
+            ctypes.byref(prob), int(dirichlet_tree), 0, int(n_charges), int(n_sources), buf, cap, ctypes.byref(n))
     _lib.check(call(None, 0), "wost_kernel_source_points")
     buf = ctypes.create_string_buffer(n.value + 1)
     _lib.check(call(buf, n.value + 1), "wost_kernel_source_points")
@@ -400,6 +416,28 @@ class WostSolver_2D:
         _lib.check(_lib.lib.wost_set_segment_tree(self._h, int(min_segments), int(leaf_segments)),
                    "wost_set_segment_tree")
 
+    def set_dirichlet_tree(self, min_segments: int | None = None, leaf_segments: int = 0):
+        """Find each step's Dirichlet distance through a segment tree over the Dirichlet
+        polyline when it has >= min_segments segments (< 0: never, 0: always, None: the
+        library's default threshold), with leaf_segments segments per leaf (0 keeps the
+        current value). Results are bit-identical to the full scan. Only the field-specialised
+        kernel uses the tree, and only for a polyline that admits it (no zero-length segment,
+        finite coordinates) and is too long to be compiled into the kernel; ``dirichlet_tree()``
+        and ``last_timing["dirichlet_tree"]`` report what holds."""
+        if min_segments is None:
+            min_segments = _lib.WOST_DTREE_MIN_SEGMENTS_DEFAULT
+        _lib.check(_lib.lib.wost_set_dirichlet_tree(self._h, int(min_segments), int(leaf_segments)),
+                   "wost_set_dirichlet_tree")
+
+    def dirichlet_tree(self) -> dict:
+        """{"min_segments", "leaf_segments", "usable", "last_solve"} (wost_dirichlet_tree_info):
+        the threshold and leaf size, whether the Dirichlet polyline admits the tree, and
+        whether the last solve's walk kernel used it."""
+        v = [ctypes.c_int32(0) for _ in range(4)]
+        _lib.check(_lib.lib.wost_dirichlet_tree_info(self._h, *[ctypes.byref(x) for x in v]), "wost_dirichlet_tree_info")
+        return {"min_segments": v[0].value, "leaf_segments": v[1].value, "usable": bool(v[2].value),
+                "last_solve": bool(v[3].value)}
+
     def set_option(self, name: str, value):
         """A kernel or launch option of this handle (include/wost.h wost_set_option: the
         walk pools, LDS staging, work-queue chunks, tree hand-outs ...). None of them
@@ -422,7 +460,9 @@ class WostSolver_2D:
     def timing(self) -> dict:
         t = _lib.WostTiming()
         _lib.check(_lib.lib.wost_last_timing(self._h, ctypes.byref(t)), "wost_last_timing")
-        return {k: getattr(t, k) for k in _TIMING_FIELDS}
+        out = {k: getattr(t, k) for k in _TIMING_FIELDS}
+        out["dirichlet_tree"] = int(self.dirichlet_tree()["last_solve"])   # (wost_dirichlet_tree_info)
+        return out
 
     def solve(self, solvePoints, nWalks=1000, maxSteps=1000, eps=1e-4, return_history=False, *,
               seed: int = 0, return_stats: bool = False):

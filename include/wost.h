@@ -47,6 +47,9 @@ extern "C" {
 /* Neumann segment-tree defaults (wost_set_segment_tree). */
 #define WOST_TREE_MIN_SEGMENTS_DEFAULT 64
 #define WOST_TREE_LEAF_DEFAULT 10
+/* Dirichlet segment-tree defaults (wost_set_dirichlet_tree). */
+#define WOST_DTREE_MIN_SEGMENTS_DEFAULT 128
+#define WOST_DTREE_LEAF_DEFAULT 10
 
 enum wost_status {
     WOST_OK = 0,
@@ -579,6 +582,23 @@ int wost_set_fixed_step_check(wost_handle* h, int32_t enable);
  * the nearest-crossing ray query). Results are bit-identical to the scans. */
 int wost_set_segment_tree(wost_handle* h, int32_t min_segments, int32_t leaf_segments);
 
+/* Dirichlet segment tree (no reference counterpart): for a Dirichlet polyline of at least
+ * min_segments segments (default WOST_DTREE_MIN_SEGMENTS_DEFAULT; < 0: never, 0: always) the
+ * field-specialised walk kernel finds each step's Dirichlet distance (geometry/
+ * PolylinesSimple.py:25-49, which scans every segment) through a tree like the Neumann one,
+ * built over the Dirichlet polyline with leaf_segments (1..32) segments per leaf (0 keeps the
+ * current value). Results are bit-identical to the scan. The tree is used only where that
+ * can be promised: never for a polyline with a zero-length segment (the scan returns NaN
+ * then), a non-finite coordinate or one above 2^60 -- such a handle keeps scanning whatever
+ * is asked here -- nor for one short enough to be compiled into the kernel; the precompiled
+ * kernels always scan. */
+int wost_set_dirichlet_tree(wost_handle* h, int32_t min_segments, int32_t leaf_segments);
+/* The handle's Dirichlet-tree state (any pointer may be NULL): its threshold and leaf size,
+ * whether its polyline admits the tree at all, and whether the last solve's walk kernel
+ * used it (0 before the first solve). */
+int wost_dirichlet_tree_info(const wost_handle* h, int32_t* min_segments, int32_t* leaf_segments, int32_t* usable,
+                             int32_t* last_solve);
+
 /* Kernel and launch options of a handle (no reference counterpart). Each selects HOW the
  * walks run -- workgroup size, LDS staging, work-queue chunks, the segment tree's walk
  * pools and hand-outs -- never what they compute: every walk's value and step count
@@ -618,6 +638,12 @@ int wost_kernel_source_sources(const wost_problem* problem, const wost_field* co
  * values and refusals): the source such a handle would build. Host only. */
 int wost_kernel_source_options(const wost_problem* problem, const char* const* names, const double* values,
                                int32_t n_options, char* out, int64_t capacity, int64_t* length);
+/* wost_kernel_source (n_charges == 0) or wost_kernel_source_points (n_charges > 0, n_sources
+ * channels) for a handle with wost_set_dirichlet_tree(min_segments, leaf_segments) called
+ * first. Host only. */
+int wost_kernel_source_dirichlet_tree(const wost_problem* problem, int32_t min_segments, int32_t leaf_segments,
+                                      int32_t n_charges, int32_t n_sources, char* out, int64_t capacity,
+                                      int64_t* length);
 
 /* The same for n_wavenumbers wavenumbers on top (wost_set_wavenumbers; 0: none, as
  * wost_kernel_source_sources), so that a machine without a GPU can generate and compile the
@@ -682,8 +708,9 @@ int wost_screened_cdf_fixed(double s, const double* rho, int64_t n, double* cdf)
  *   op 3 rayIntersection   (:104-132, :281-292) out_f[n][nv-1]  (dirs used)
  *   op 4 intersectPolylines(:134-197, :294-307) out_f[n][5] = x, y, nx, ny, found
  *                                                (dirs and radii used)
- * op | WOST_GEOM_TREE (ops 2 and 4, >= 2 segments): the same query answered by the
- * walk kernels' Neumann segment tree (wost_set_segment_tree; default leaf size) one
+ * op | WOST_GEOM_TREE (ops 0, 2 and 4, >= 2 segments): the same query answered by the
+ * walk kernels' segment tree (ops 2, 4: wost_set_segment_tree; op 0: wost_set_dirichlet_tree,
+ * refused for a polyline that does not admit it; default leaf sizes) one
  * query per lane instead of the full scan -- bit-identical to the scan, which the
  * tests check at the reference's own outputs (tests/golden/geometry_kats_c5.npz). */
 enum wost_geom_op {
