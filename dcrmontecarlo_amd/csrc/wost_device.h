@@ -441,7 +441,11 @@ WOST_HD float fv_sigmoid_radial(float x, float y, float k, float cx, float cy, f
     const bool out = d2 >= sat.hi2, in = d2 <= sat.lo2;
     WOST_VOTE(4, !(out || in));
     if (WOST_SAT_ALL(out || in)) return out ? sat.s_out : sat.s_in;
-    return sigmoidf(k * (f_sqrt(d2) - R));
+    // the distance as fj_sigmoid_radial forms it, so that the value is the jet's bit for bit
+    // (sqrt(d2) rounds differently: tests/test_field_zoo.py)
+    const float inv = f_rsq(d2);
+    const float d = d2 > 0.f ? d2 * inv : 0.f;
+    return sigmoidf(k * (d - R));
 }
 WOST_HD float fv_ind_box(float x, float y, float x0, float x1, float y0, float y1) {
     return (x >= x0 && x <= x1 && y >= y0 && y <= y1) ? 1.0f : 0.0f;
@@ -505,21 +509,26 @@ WOST_HD Jet fj_sigmoid_radial(float x, float y, float k, float cx, float cy, flo
     float d2 = dx * dx + dy * dy;
     const RadialSat sat = radial_saturation(k, R);
     const bool out = d2 >= sat.hi2, in = d2 <= sat.lo2;
-    float inv, s;
+    float inv, inv_lap, s;
     WOST_VOTE(6, !(out || in));
     if (WOST_SAT_ALL(out || in)) {
         // s1 = s2 = 0: inv only carries its sign (+) and rsq(0) = +inf into the derivatives
         inv = d2 > 0.f ? 1.0f : WOST_INF;
+        inv_lap = inv;
         s = out ? sat.s_out : sat.s_in;
     } else {
         inv = f_rsq(d2);               // one transcendental for d and 1/d
         float d = d2 > 0.f ? d2 * inv : 0.f;
         s = sigmoidf(k * (d - R));
+        // exactly at the centre the gradient is 0 * inf = NaN; the Laplacian is NaN too, as the
+        // reference's autograd gives it (s1 k / 0 alone would be an infinity, which sigma'
+        // turns into NaN anyway through the gradient): tests/field_zoo.py, the radial centre
+        inv_lap = d2 > 0.f ? inv : WOST_NAN;
     }
     float s1 = s * (1.f - s);          // ds/dz
     float s2 = s1 * (1.f - 2.f * s);   // d2s/dz2
     // z = k (d - R): grad z = k (x-c)/d, lap z = k/d (2-D), |grad z|^2 = k^2
-    return Jet{s, s1 * k * dx * inv, s1 * k * dy * inv, s2 * k * k + s1 * k * inv};
+    return Jet{s, s1 * k * dx * inv, s1 * k * dy * inv, s2 * k * k + s1 * k * inv_lap};
 }
 // ---- whole-field saturation (the specialised kernels' alpha jets) ------------
 // When every factor of a field is saturated at a point -- sharp sigmoids exactly
