@@ -40,6 +40,81 @@
 #define WOST_NO_SPECULATION() ((void)0)
 #endif
 
+// Wave votes on scalar masks. WOST_ANY(c) on a bool that reaches the vote from another
+// block (a flag carried round a loop, a condition set on two paths, a select) compiles to
+// a round trip through a VGPR: v_cndmask 0/1 from the lane mask, v_cmp_ne back to a mask,
+// then the scalar test. A WaveMask is the lane mask itself: a compare helper forms it in
+// one v_cmp (the lanes that are here and for which the compare holds), masks combine in
+// scalar registers, and a vote is a scalar test of the result. Form and combine masks only
+// where their lanes are all present (never update one inside divergent code: it would turn
+// into a VGPR pair); a mask may be formed in one block and voted on in another.
+//   wm_gt / wm_ge / wm_lt / wm_le / wm_eq   float compares (ordered: false on a NaN)
+//   wm_lt_i (signed), wm_lt_u / wm_le_u     integer compares
+//   wm_and, wm_or, wm_andn (a & ~b), wm_not (the lanes here that are not in m), wm_none
+//   wm_any, wm_all                          the votes; wm_ballot: the mask as 64 bits
+//   wm_lane(m)                              this lane's bit as a bool (no instruction where the
+//                                           compiler has the inverse-ballot builtin)
+// The host build of the header has one lane: a WaveMask is that lane's bool.
+#if defined(__HIP_DEVICE_COMPILE__)
+namespace wost {
+using WaveMask = uint64_t;
+// (the predicate numbers of the compiler's compare builtins: ordered float 1-5, integer 36-40)
+WOST_HD WaveMask wm_eq(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 1); }
+WOST_HD WaveMask wm_gt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 2); }
+WOST_HD WaveMask wm_ge(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 3); }
+WOST_HD WaveMask wm_lt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 4); }
+WOST_HD WaveMask wm_le(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 5); }
+WOST_HD WaveMask wm_lt_u(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 36); }
+WOST_HD WaveMask wm_le_u(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 37); }
+WOST_HD WaveMask wm_lt_i(int32_t a, int32_t b) { return __builtin_amdgcn_sicmp(a, b, 40); }
+WOST_HD WaveMask wm_none() { return 0ull; }
+WOST_HD WaveMask wm_here() { return __builtin_amdgcn_ballot_w64(true); }
+WOST_HD WaveMask wm_not(WaveMask m) { return wm_here() & ~m; }
+WOST_HD bool wm_any(WaveMask m) { return m != 0ull; }
+WOST_HD bool wm_all(WaveMask m) { return wm_not(m) == 0ull; }
+WOST_HD uint64_t wm_ballot(WaveMask m) { return m; }
+WOST_HD bool wm_lane(WaveMask m) {
+#if __has_builtin(__builtin_amdgcn_inverse_ballot_w64)
+    return __builtin_amdgcn_inverse_ballot_w64(m);
+#else   // an older compiler (the hiprtc that PyTorch-ROCm bundles): the lane's bit by a shift
+    return ((m >> __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))) & 1ull) != 0ull;
+#endif
+}
+// the same mask, read from the first lane: for a mask carried round a loop that the compiler
+// keeps as a per-lane value, so that what is computed from it is scalar again
+WOST_HD WaveMask wm_scalar(WaveMask m) {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32)) << 32 |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
+}
+#else
+namespace wost {
+using WaveMask = bool;
+WOST_HD WaveMask wm_eq(float a, float b) { return a == b; }
+WOST_HD WaveMask wm_gt(float a, float b) { return a > b; }
+WOST_HD WaveMask wm_ge(float a, float b) { return a >= b; }
+WOST_HD WaveMask wm_lt(float a, float b) { return a < b; }
+WOST_HD WaveMask wm_le(float a, float b) { return a <= b; }
+WOST_HD WaveMask wm_lt_u(uint32_t a, uint32_t b) { return a < b; }
+WOST_HD WaveMask wm_le_u(uint32_t a, uint32_t b) { return a <= b; }
+WOST_HD WaveMask wm_lt_i(int32_t a, int32_t b) { return a < b; }
+WOST_HD WaveMask wm_none() { return false; }
+WOST_HD WaveMask wm_here() { return true; }
+WOST_HD WaveMask wm_not(WaveMask m) { return !m; }
+WOST_HD bool wm_any(WaveMask m) { return m; }
+WOST_HD bool wm_all(WaveMask m) { return m; }
+WOST_HD uint64_t wm_ballot(WaveMask m) { return m ? 1ull : 0ull; }
+WOST_HD bool wm_lane(WaveMask m) { return m; }
+WOST_HD WaveMask wm_scalar(WaveMask m) { return m; }
+#endif
+WOST_HD WaveMask wm_and(WaveMask a, WaveMask b) { return a & b; }
+WOST_HD WaveMask wm_or(WaveMask a, WaveMask b) { return a | b; }
+#if defined(__HIP_DEVICE_COMPILE__)
+WOST_HD WaveMask wm_andn(WaveMask a, WaveMask b) { return a & ~b; }
+#else
+WOST_HD WaveMask wm_andn(WaveMask a, WaveMask b) { return a && !b; }
+#endif
+}  // namespace wost
+
 // Study builds (option vote_stats: the generated kernel defines WOST_VOTE_STATS): how often
 // each wave vote's slow side runs. WOST_VOTE(site, c) stands before the vote on c and
 // counts, per wave, the times it ran, the times some lane had c, and the lanes that had
@@ -292,14 +367,14 @@ constexpr float kClipRatio = 0x1.00002p+0f;
 constexpr float kClipFloor = 0x1p-100f;
 
 WOST_HD bool norm_greater(float a2, float b2) {
-    const bool sure = a2 > b2 * kClipRatio && b2 >= kClipFloor;
-    const bool band = a2 > b2 && !sure;
-    bool r = sure;
+    const WaveMask sure = wm_and(wm_gt(a2, b2 * kClipRatio), wm_ge(b2, kClipFloor));
+    const WaveMask band = wm_andn(wm_gt(a2, b2), sure);
+    bool r = wm_lane(sure);
     // a real branch: if-converted, both correctly rounded roots come back for every lane
-    WOST_VOTE(2, band);
-    if (WOST_ANY(band)) {
+    WOST_VOTE(2, wm_lane(band));
+    if (wm_any(band)) {
         WOST_NO_SPECULATION();
-        if (band) r = sqrtf(a2) > sqrtf(b2);
+        if (wm_lane(band)) r = sqrtf(a2) > sqrtf(b2);
     }
     return r;
 }
@@ -405,7 +480,7 @@ WOST_HD RadialSat radial_saturation(float k, float R) {
 #if defined(WOST_NO_SATURATION_SHORTCUTS)
 #define WOST_SAT_ALL(c) false
 #else
-#define WOST_SAT_ALL(c) (!WOST_ANY(!(c)))
+#define WOST_SAT_ALL(m) wost::wm_all(m)   // m: a WaveMask
 #endif
 constexpr float kExpZeroBelow = -110.0f;
 
@@ -423,7 +498,7 @@ WOST_HD float fv_exp_quad_diag(float x, float y, float cx, float cy, float axx, 
     const float q = axx * (dx * dx) + ayy * (dy * dy);
     float e = 0.0f;
     WOST_VOTE(3, !(q < kExpZeroBelow));
-    if (!WOST_SAT_ALL(q < kExpZeroBelow)) {
+    if (!WOST_SAT_ALL(wm_lt(q, kExpZeroBelow))) {
         WOST_NO_SPECULATION();
         e = f_exp(q);
     }
@@ -438,9 +513,10 @@ WOST_HD float fv_sigmoid_radial(float x, float y, float k, float cx, float cy, f
     float dx = x - cx, dy = y - cy;
     const float d2 = dx * dx + dy * dy;
     const RadialSat sat = radial_saturation(k, R);
-    const bool out = d2 >= sat.hi2, in = d2 <= sat.lo2;
-    WOST_VOTE(4, !(out || in));
-    if (WOST_SAT_ALL(out || in)) return out ? sat.s_out : sat.s_in;
+    const WaveMask mout = wm_ge(d2, sat.hi2), min_ = wm_le(d2, sat.lo2);
+    const bool out = wm_lane(mout);
+    WOST_VOTE(4, !(out || wm_lane(min_)));
+    if (WOST_SAT_ALL(wm_or(mout, min_))) return out ? sat.s_out : sat.s_in;
     // the distance as fj_sigmoid_radial forms it, so that the value is the jet's bit for bit
     // (sqrt(d2) rounds differently: tests/test_field_zoo.py)
     const float inv = f_rsq(d2);
@@ -483,7 +559,7 @@ WOST_HD Jet fj_exp_quad_diag(float x, float y, float cx, float cy, float axx, fl
     const float q = axx * (dx * dx) + ayy * (dy * dy);
     float e = 0.0f;
     WOST_VOTE(5, !(q < kExpZeroBelow));
-    if (!WOST_SAT_ALL(q < kExpZeroBelow)) {
+    if (!WOST_SAT_ALL(wm_lt(q, kExpZeroBelow))) {
         WOST_NO_SPECULATION();
         e = f_exp(q);
     }
@@ -508,10 +584,11 @@ WOST_HD Jet fj_sigmoid_radial(float x, float y, float k, float cx, float cy, flo
     float dx = x - cx, dy = y - cy;
     float d2 = dx * dx + dy * dy;
     const RadialSat sat = radial_saturation(k, R);
-    const bool out = d2 >= sat.hi2, in = d2 <= sat.lo2;
+    const WaveMask mout = wm_ge(d2, sat.hi2), min_ = wm_le(d2, sat.lo2);
+    const bool out = wm_lane(mout);
     float inv, inv_lap, s;
-    WOST_VOTE(6, !(out || in));
-    if (WOST_SAT_ALL(out || in)) {
+    WOST_VOTE(6, !(out || wm_lane(min_)));
+    if (WOST_SAT_ALL(wm_or(mout, min_))) {
         // s1 = s2 = 0: inv only carries its sign (+) and rsq(0) = +inf into the derivatives
         inv = d2 > 0.f ? 1.0f : WOST_INF;
         inv_lap = inv;
@@ -541,25 +618,26 @@ WOST_HD Jet fj_sigmoid_radial(float x, float y, float k, float cx, float cy, flo
 // derivative arithmetic. Each predicate keeps a margin to the thresholds its
 // factor's own shortcut uses (radial_saturation; z >= 20 / <= -90; q < -110), so
 // a saturated lane is one whose full jet is saturated whatever the rounding.
-WOST_HD bool sat_sigmoid_radial(float x, float y, float k, float cx, float cy, float R, bool& centre) {
+// Each returns its lanes as a WaveMask (the generated jet votes on their conjunction).
+WOST_HD WaveMask sat_sigmoid_radial(float x, float y, float k, float cx, float cy, float R, bool& centre) {
     const float dx = x - cx, dy = y - cy;
     const float d2 = dx * dx + dy * dy;
     const RadialSat sat = radial_saturation(k, R);
     centre = centre || !(d2 > 0.0f);
-    return d2 >= sat.hi2 || d2 <= sat.lo2;
+    return wm_or(wm_ge(d2, sat.hi2), wm_le(d2, sat.lo2));
 }
-WOST_HD bool sat_sigmoid_lin(float x, float y, float a, float b, float c) {
+WOST_HD WaveMask sat_sigmoid_lin(float x, float y, float a, float b, float c) {
     const float z = a * x + b * y + c;
-    return z >= 21.0f || z <= -91.0f;
+    return wm_or(wm_ge(z, 21.0f), wm_le(z, -91.0f));
 }
-WOST_HD bool sat_exp_quad_diag(float x, float y, float cx, float cy, float axx, float ayy) {
+WOST_HD WaveMask sat_exp_quad_diag(float x, float y, float cx, float cy, float axx, float ayy) {
     const float dx = x - cx, dy = y - cy;
-    return axx * (dx * dx) + ayy * (dy * dy) < kExpZeroBelow - 1.0f;
+    return wm_lt(axx * (dx * dx) + ayy * (dy * dy), kExpZeroBelow - 1.0f);
 }
-WOST_HD bool sat_exp_quad(float x, float y, float cx, float cy, float axx, float ayy, float axy, float ax, float ay,
+WOST_HD WaveMask sat_exp_quad(float x, float y, float cx, float cy, float axx, float ayy, float axy, float ax, float ay,
                           float a0) {
     const float dx = x - cx, dy = y - cy;
-    return axx * (dx * dx) + ayy * (dy * dy) + axy * (dx * dy) + ax * dx + ay * dy + a0 < kExpZeroBelow - 1.0f;
+    return wm_lt(axx * (dx * dx) + ayy * (dy * dy) + axy * (dx * dy) + ax * dx + ay * dy + a0, kExpZeroBelow - 1.0f);
 }
 
 WOST_HD Jet fj_ind_box(float x, float y, float x0, float x1, float y0, float y1) {
@@ -778,6 +856,12 @@ WOST_HD bool flat_lane(float z) { return z == 0.0f; }
 WOST_HD bool flat_sigma_trivial(bool flat, float alpha_v, float alpha_min) {
     return flat && alpha_v >= alpha_min;
 }
+// The same as a wave mask, for the walk's vote. `flat` reaches the walk from the jet's two
+// returns, so a vote on it would go through a VGPR and back; it is folded instead into the
+// bound's compare, as the operand's NaN (one select).
+WOST_HD WaveMask flat_sigma_trivial_lanes(bool flat, float alpha_v, float alpha_min) {
+    return wm_ge(flat ? alpha_v : WOST_NAN, alpha_min);
+}
 
 // ---------------------------------------------------------------------------
 // Screened Green's function norm (solvers/utils.py:29-44):
@@ -947,7 +1031,7 @@ WOST_HD float poly_distance(VP v, int nv, float px, float py) {
 template <class VP>
 WOST_HD float poly_distance_const(VP v, const float* rcp, int nv, float px, float py) {
 #pragma clang fp contract(off)
-    bool redo = !(fabsf(px) <= 0x1p60f && fabsf(py) <= 0x1p60f);   // also catches NaN
+    const WaveMask in_range = wm_and(wm_le(fabsf(px), 0x1p60f), wm_le(fabsf(py), 0x1p60f));   // false on a NaN
     float qmin = WOST_INF, qmax = 0.0f;   // range of |q| over the Markstein segments
     float best = WOST_INF;
     float2 a = v[0];
@@ -974,11 +1058,11 @@ WOST_HD float poly_distance_const(VP v, const float* rcp, int nv, float px, floa
         best = fminf(best, ex * ex + ey * ey);
         a = b;
     }
-    redo |= !(qmin >= 0x1p-40f && qmax <= 0x1p40f);
+    const WaveMask redo = wm_not(wm_and(in_range, wm_and(wm_ge(qmin, 0x1p-40f), wm_le(qmax, 0x1p40f))));
     float d = sqrt_rn(best);
-    WOST_VOTE(8, redo);
-    if (WOST_ANY(redo)) {
-        if (redo) d = poly_distance(v, nv, px, py);
+    WOST_VOTE(8, wm_lane(redo));
+    if (wm_any(redo)) {
+        if (wm_lane(redo)) d = poly_distance(v, nv, px, py);
     }
     return d;
 }
@@ -1102,9 +1186,10 @@ WOST_HD void unit_direction(float dxi, float dyi, float& dn, float& dx, float& d
     const float s2 = dxi * dxi + dyi * dyi;
     const int32_t k = __builtin_bit_cast(int32_t, s2) - 0x3F800000;
 #if defined(WOST_EXP_IEEE_DIRECTION)
-    const bool fast = false;
+    const WaveMask slow = wm_here();
 #else
-    const bool fast = (uint32_t)(k + 64) <= 128u && fabsf(dxi) >= 0x1p-100f && fabsf(dyi) >= 0x1p-100f;
+    const WaveMask slow = wm_not(wm_and(wm_le_u((uint32_t)(k + 64), 128u),
+                                        wm_and(wm_ge(fabsf(dxi), 0x1p-100f), wm_ge(fabsf(dyi), 0x1p-100f))));
 #endif
     // (the patterns of a lane that is not fast are not used; unsigned where its j would overflow)
     const int32_t nb = (int32_t)((__builtin_bit_cast(uint32_t, s2) + 0x3F800000u) >> 1);
@@ -1116,9 +1201,9 @@ WOST_HD void unit_direction(float dxi, float dyi, float& dn, float& dx, float& d
     dn = n;
     dx = fmaf(fmaf(-qx, n, dxi), y, qx);
     dy = fmaf(fmaf(-qy, n, dyi), y, qy);
-    WOST_VOTE(10, !fast);
-    if (WOST_ANY(!fast)) {
-        if (!fast) {
+    WOST_VOTE(10, wm_lane(slow));
+    if (wm_any(slow)) {
+        if (wm_lane(slow)) {
             dn = sqrtf(s2);
             dx = dxi / dn;
             dy = dyi / dn;

@@ -329,8 +329,8 @@ std::string jet_body(const DField& fd, const DTerm* terms, const DFactor* factor
         if (!sat.empty()) {
             o << "        {\n"
               << "            bool centre = false;\n"
-              << "            const bool sat = " << sat << ";\n"
-              << ((xflags & kVoteStatsFlag) ? "            WOST_VOTE(12, !sat);\n" : "")
+              << "            const wost::WaveMask sat = " << sat << ";\n"   // the factors' lane masks, and-ed
+              << ((xflags & kVoteStatsFlag) ? "            WOST_VOTE(12, !wost::wm_lane(sat));\n" : "")
               << "            if (WOST_SAT_ALL(sat)) {\n";
             o << "                const float z = " << (radial ? "centre ? __builtin_nanf(\"\") : 0.0f" : "0.0f")
               << ";\n"

@@ -911,8 +911,9 @@ __device__ __forceinline__ Hit intersect_polylines_tree_wave(const SegTree& t, f
 #ifndef WOST_POOL_MIN_PUSH
 #define WOST_POOL_MIN_PUSH 1
 #endif
-__device__ __forceinline__ bool pool_near(float4 b, float x, float y) {
-    return x >= b.x && x <= b.z && y >= b.y && y <= b.w;
+// the lanes whose walk is inside the near box, as a wave mask (wost_device.h WaveMask)
+__device__ __forceinline__ WaveMask pool_near_lanes(float4 b, float x, float y) {
+    return wm_and(wm_and(wm_ge(x, b.x), wm_le(x, b.z)), wm_and(wm_ge(y, b.y), wm_le(y, b.w)));
 }
 // walks parked in class c (header word 1 + c), read with an atomic load so that every
 // read goes to memory (under the lock: exact; outside it: a hint)
@@ -1089,8 +1090,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     const float flat_amin = kFlatSigmaPrime ? flat_alpha_min(inv_sb) : 0.0f;
 
     const int lane = threadIdx.x & 63;
-    const uint64_t lanebit = 1ull << lane;
-    const uint64_t lanes_below = lanebit - 1ull;
+    const uint64_t lanes_below = (1ull << lane) - 1ull;
 #if defined(WOST_VOTE_STATS)   // study build: the wave votes' counters (wost_device.h WOST_VOTE)
     vote_begin();
 #endif
@@ -1120,8 +1120,12 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         c_end = min(c_next + (uint64_t)A.chunk0, cnt);
     }
 
+    // the lanes that hold a walk, as a wave mask in scalar registers (wost_device.h
+    // WaveMask): the votes below test it directly, a lane reads its own bit with wm_lane,
+    // and it changes only where the whole wave is present (after the termination, at a
+    // refill round, at a pool exchange), from the masks of the lanes that end or start there
+    WaveMask live = wm_none();
     // per-lane walk state (solvers/WoStSolver.py:188-195)
-    bool active = false;
     uint64_t wid = 0;           // global walk id: the Philox subsequence
     PhiloxWalk pw{0u, 0u, 0u, 0u};   // its per-walk Philox words (philox_walk)
     uint64_t lid = 0;           // local walk index: the output slot
@@ -1157,9 +1161,15 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     // so neither do its bits.
     constexpr bool kBatchEnd = TREE;
     for (;;) {
-        const bool done = active && !((k < A.max_steps) && (dD > A.eps));
+        // (the compiler carries the mask round this loop as a per-lane value, since the refill's
+        // lane-dependent branches end where the loop's paths merge: read back as a scalar, what is
+        // formed from it in this iteration stays in scalar registers)
+        live = wm_scalar(live);
+        const WaveMask done_m = wm_andn(live, wm_and(wm_lt_i(k, A.max_steps), wm_gt(dD, A.eps)));
+        const bool done = wm_lane(done_m);
         bool batch = true;
-        if (kBatchEnd) batch = __popcll(__ballot(done || !active)) >= WOST_REFILL_MIN || !__any(active && !done);
+        if (kBatchEnd)
+            batch = __popcll(wm_ballot(wm_or(done_m, wm_not(live)))) >= WOST_REFILL_MIN || !wm_any(wm_andn(live, done_m));
         // --- walk termination: while-condition of :206, boundary term :295-298
         if (batch && done) {
             const float g0 = fld.has_g() ? fld.g(px, py) : 0.0f;
@@ -1180,8 +1190,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             for (int c = 0; c < NC; ++c) A.out_val[li * NC + c] = total[c];
             A.out_steps[li] = (uint32_t)k;
             if (kWaveStats) my_kmax = (uint32_t)k > my_kmax ? (uint32_t)k : my_kmax;
-            active = false;
         }
+        if (batch) live = wm_andn(live, done_m);   // the finished lanes are idle
 
         // --- refill idle lanes from the wave's chunk (active-mask compaction), in
         // batches: the refill runs on the few lanes it starts while the wave's other
@@ -1196,11 +1206,13 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         // the wave's own class first, then new walks from the queue. A walk's state moves
         // with it whole and its result depends only on its id: the bits do not change.
         if (pool != nullptr && batch) {
-            const uint64_t act = __ballot(active);
-            const uint64_t nm = __ballot(active && pool_near(A.pool_box, px, py));
+            const uint64_t act = wm_ballot(live);
+            const uint64_t nm = wm_ballot(wm_and(live, pool_near_lanes(A.pool_box, px, py)));
             const int nact = __popcll(act), nnear = __popcll(nm);
             const uint32_t hn = pool_count(pool, 0), hf = pool_count(pool, 1);
-            const int role = A.pool_near_waves > 0 ? ((int)(threadIdx.x >> 6) < A.pool_near_waves ? 0 : 1)
+            // (the wave's index as a scalar: the exchange below updates `live`, which must stay uniform)
+            const int wave_in_group = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+            const int role = A.pool_near_waves > 0 ? (wave_in_group < A.pool_near_waves ? 0 : 1)
                              : nact > 0 ? (2 * nnear > nact ? 0 : 1) : (hn >= hf ? 0 : 1);
             uint64_t mis = role == 0 ? (act & ~nm) : nm;
             if (exhausted || __popcll(mis) < WOST_POOL_MIN_PUSH) mis = 0ull;
@@ -1210,7 +1222,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 const int cm = 1 - role;
                 const uint32_t npush = min((uint32_t)__popcll(mis), (uint32_t)A.pool_slots - cnt[cm]);
                 const uint32_t rk = (uint32_t)__popcll(mis & lanes_below);
-                if ((mis & lanebit) && rk < npush) {
+                const WaveMask pushed = wm_and(mis, wm_lt_u(rk, npush));
+                if (wm_lane(pushed)) {
                     uint32_t* const r = pool + 4 + (size_t)cm * pool_fields(NS) * A.pool_slots + cnt[cm] + rk;
                     const int P = A.pool_slots;
                     r[0 * P] = (uint32_t)wid; r[1 * P] = (uint32_t)(wid >> 32);
@@ -1222,13 +1235,16 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     r[10 * P] = __builtin_bit_cast(uint32_t, ax[0]);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) r[(11 + s) * P] = __builtin_bit_cast(uint32_t, total[s]);
-                    active = false;
                 }
+                // (wm_scalar here and below: after a lane-dependent branch the compiler takes the
+                // masks merged at its end for per-lane values)
+                live = wm_scalar(wm_andn(live, pushed));
                 cnt[cm] += npush;
-                const uint64_t fr = __ballot(!active);
+                const uint64_t fr = wm_ballot(wm_not(live));
                 const uint32_t npull = min((uint32_t)__popcll(fr), cnt[role]);
                 const uint32_t rf = (uint32_t)__popcll(fr & lanes_below);
-                if (!active && rf < npull) {
+                const WaveMask pulled = wm_and(fr, wm_lt_u(rf, npull));
+                if (wm_lane(pulled)) {
                     const uint32_t* const r =
                         pool + 4 + (size_t)role * pool_fields(NS) * A.pool_slots + (cnt[role] - npull) + rf;
                     const int P = A.pool_slots;
@@ -1244,14 +1260,14 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     for (int s = 0; s < NS; ++s) total[s] = __builtin_bit_cast(float, r[(11 + s) * P]);
                     pw = philox_walk(wid, A.key0, A.key1);
                     if (WOST_PHILOX_AHEAD) rn_ahead = philox_draw(pw, (uint32_t)k, A.key0, A.key1);
-                    active = true;
                 }
+                live = wm_scalar(wm_or(live, pulled));
                 cnt[role] -= npull;
                 pool_unlock(pool, lane, cnt[0], cnt[1]);
             }
         }
-        uint64_t need = batch ? __ballot(!active) : 0ull;
-        if (!kBatchEnd && __popcll(need) < WOST_REFILL_MIN && __any(active)) need = 0ull;
+        uint64_t need = batch ? wm_ballot(wm_not(live)) : 0ull;
+        if (!kBatchEnd && __popcll(need) < WOST_REFILL_MIN && wm_any(live)) need = 0ull;
         while (need != 0ull && !exhausted) {
             if (c_next >= c_end) {
                 if (A.queue_base >= A.count) {   // the static chunks covered every walk
@@ -1295,7 +1311,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             const uint32_t n = (uint32_t)__popcll(need);
             const uint32_t take = avail < (uint64_t)n ? (uint32_t)avail : n;
             const uint32_t rank = (uint32_t)__popcll(need & lanes_below);
-            if ((need & lanebit) && rank < take) {
+            const WaveMask got = wm_and(need, wm_lt_u(rank, take));   // the lanes that start a walk
+            if (wm_lane(got)) {
                 lid = c_next + rank;
                 uint64_t pid;
                 WOST_WALK_OF_LOCAL(A, lid, wid, pid)
@@ -1322,28 +1339,29 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
 #pragma unroll
                     for (int m = 1; m < NM; ++m) ax[m] = A.point_alpha[(size_t)m * (size_t)A.n_points + pid];
                 }
-                active = true;
             }
+            live = wm_or(live, got);
             c_next += take;
             if (kAdaptive) {
                 q_taken += take;
                 WOST_KEEP_VGPR(q_taken);
             }
-            need = __ballot(!active);
+            need = wm_ballot(wm_andn(need, got));   // (need was every idle lane: the loop runs only then)
         }
         // the queue is exhausted: idle lanes take parked walks of either class, and the
         // wave ends only when both pools are empty (a wave parks walks only while the
         // queue is not exhausted for it, and drains the pools itself before it ends)
-        if (pool != nullptr && exhausted && batch && __ballot(!active) != 0ull &&
-            (!__any(active) || pool_count(pool, 0) + pool_count(pool, 1) > 0u)) {
+        if (pool != nullptr && exhausted && batch && wm_any(wm_not(live)) &&
+            (!wm_any(live) || pool_count(pool, 0) + pool_count(pool, 1) > 0u)) {
             pool_lock(pool, lane);
             uint32_t cnt[2] = {pool_count(pool, 0), pool_count(pool, 1)};
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const uint64_t fr = __ballot(!active);
+                const uint64_t fr = wm_ballot(wm_not(live));
                 const uint32_t npull = min((uint32_t)__popcll(fr), cnt[c]);
                 const uint32_t rf = (uint32_t)__popcll(fr & lanes_below);
-                if (!active && rf < npull) {
+                const WaveMask pulled = wm_and(fr, wm_lt_u(rf, npull));
+                if (wm_lane(pulled)) {
                     const uint32_t* const r =
                         pool + 4 + (size_t)c * pool_fields(NS) * A.pool_slots + (cnt[c] - npull) + rf;
                     const int P = A.pool_slots;
@@ -1359,23 +1377,30 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                     for (int s = 0; s < NS; ++s) total[s] = __builtin_bit_cast(float, r[(11 + s) * P]);
                     pw = philox_walk(wid, A.key0, A.key1);
                     if (WOST_PHILOX_AHEAD) rn_ahead = philox_draw(pw, (uint32_t)k, A.key0, A.key1);
-                    active = true;
                 }
+                live = wm_scalar(wm_or(live, pulled));
                 cnt[c] -= npull;
             }
             pool_unlock(pool, lane, cnt[0], cnt[1]);
         }
-        if (!__any(active)) break;
+        if (!wm_any(live)) break;
         if (kWaveStats) {
             q_iters += 1u;
             WOST_KEEP_VGPR(q_iters);
         }
         // a freshly refilled walk may already fail the while-condition (eps >= 1,
         // maxSteps == 0): it takes no step and is finished at the next iteration
-        bool stepping = active && (k < A.max_steps) && (dD > A.eps);
+        bool stepping;
         // the cooperative tree queries need every lane of the wave: the others run the
         // step's pure arithmetic up to the ray query with them and leave after it
-        if (kWaveTree ? !__any(stepping) : !stepping) continue;
+        if constexpr (kWaveTree) {
+            const WaveMask step_m = wm_and(live, wm_and(wm_lt_i(k, A.max_steps), wm_gt(dD, A.eps)));
+            stepping = wm_lane(step_m);
+            if (!wm_any(step_m)) continue;
+        } else {
+            stepping = wm_lane(live) && (k < A.max_steps) && (dD > A.eps);
+            if (!stepping) continue;
+        }
 
         // --- one walk-step (:206-291)
 #if defined(WOST_TREE_ITER_STATS)
@@ -1782,9 +1807,10 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
             for (int j = 0; j < NW; ++j) sc[j] = 1.0f;
             bool sp_wave = true;                                     // (see the FIX branch above)
             if constexpr (kFlatSigmaPrime) {
-                const bool full = !accept && !flat_sigma_trivial(aj_flat, aj.v, flat_amin);
-                WOST_VOTE(13, full);
-                sp_wave = WOST_ANY(full);
+                const WaveMask full =
+                    wm_andn(wm_not(wm_gt(mu, sigma_bar * gnorm)), flat_sigma_trivial_lanes(aj_flat, aj.v, flat_amin));
+                WOST_VOTE(13, wm_lane(full));
+                sp_wave = wm_any(full);
             }
 #if defined(WOST_ABL_NO_SIGMA_PRIME)
             if (false) {

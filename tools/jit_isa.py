@@ -4,7 +4,7 @@
 Generates the kernel source libwost would hand to hiprtc (wost_kernel_source),
 compiles it with hipcc for gfx950 with hiprtc's options, and prints the
 kernel's resource usage and an instruction histogram (static counts).
-Usage: python tools/jit_isa.py dcr_dipole [--out build/jit] [--show] [--wavenumbers NK] [--sources NS]
+Usage: python tools/jit_isa.py dcr_dipole [--out build/jit] [--show] [--votes] [--wavenumbers NK] [--sources NS]
        [--point-charges PC]   (point sources: PC charges in NS sources, compat="fixed")
        [--models M]           (set_models: the scenario's fields, a constant background, then perturbed copies)"""
 import argparse
@@ -17,12 +17,76 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+_CND = re.compile(r"^v_cndmask_b32(?:_e32|_e64)?\s+(v\d+),\s*0,\s*1(?:,\s*(?:vcc|s\[\d+:\d+\]))?$")
+_CMP = re.compile(r"^v_cmp_ne_u32(?:_e32|_e64)?\s+(?:vcc|s\[\d+:\d+\]),\s*0,\s*(v\d+)$")
+
+
+def instructions(body):
+    """(line number, text, in a loop) of every instruction of a function body."""
+    out, in_loop = [], False
+    for n, line in enumerate(body.splitlines(), 1):
+        code, _, note = line.partition(";")
+        s = code.strip()
+        if s.endswith(":") or (not s and note.lstrip().startswith("%bb.")):   # a block starts
+            in_loop = "in Loop:" in note or "Loop Header:" in note
+        if not s or s.startswith((".", "//")) or s.endswith(":"):
+            continue
+        out.append((n, s, in_loop))
+    return out
+
+
+def round_trips(body):
+    """The wave votes that send a lane mask through a VGPR and back: a v_cndmask_b32 vN, 0, 1, <mask>
+    whose vN is next read by a v_cmp_ne_u32 <mask>, 0, vN. (The 0/1 selects of the walk-id arithmetic
+    are read by other instructions.) Returns [(line, select, line, compare)]."""
+    ins = instructions(body)
+    found = []
+    for i, (n, s, _) in enumerate(ins):
+        m = _CND.match(s)
+        if not m:
+            continue
+        reg = re.compile(r"\b" + m.group(1) + r"\b")
+        for n2, s2, _ in ins[i + 1:]:
+            if reg.search(s2):
+                m2 = _CMP.match(s2)
+                if m2 and m2.group(1) == m.group(1):
+                    found.append((n, s, n2, s2))
+                break
+    return found
+
+
+def loop_valu(body):
+    """Static count of the VALU instructions inside the function's loops."""
+    return sum(1 for _, s, in_loop in instructions(body) if in_loop and s.startswith("v_"))
+
+
+def assemble(hip):
+    """Compiles a generated kernel source to gfx950 assembly with hiprtc's options (next to it, .s);
+    returns the assembly and the body of wost_walk_jit."""
+    asm = os.path.splitext(hip)[0] + ".s"
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--offload-device-only", "-S", "-O3", "-std=c++17",
+           "-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=fast-honor-pragmas",
+           *([] if os.environ.get("WOST_JIT_SLP") == "1" else ["-fno-slp-vectorize"]),
+           "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "dcrmontecarlo_amd", "csrc"), hip, "-o", asm]
+    subprocess.run(cmd, check=True)
+    text = open(asm).read()
+    return text, text.split("wost_walk_jit:", 1)[1].split(".Lfunc_end", 1)[0]
+
+
+def resources(text):
+    """The kernel's resource usage from the assembly's metadata."""
+    keys = ("vgpr_count", "sgpr_count", "lds_size", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")
+    found = {k: re.search(rf"\.{k}:\s+(\d+)", text) for k in keys}
+    return {k: int(m.group(1)) for k, m in found.items() if m}
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("scenario")
     ap.add_argument("--out", default=os.path.join(REPO, "build", "jit"))
     ap.add_argument("--show", action="store_true", help="print the ISA")
+    ap.add_argument("--votes", action="store_true",
+                    help="list the wave votes that still go through a VGPR (v_cndmask 0/1, v_cmp_ne), by body line")
     ap.add_argument("--waves", default=None, help="WOST_JIT_WAVES for the generator")
     ap.add_argument("--wavenumbers", type=int, default=0, help="NK: wavenumbers per walk (set_wavenumbers; 0: none)")
     ap.add_argument("--sources", type=int, default=0, help="NS: copies of the scenario's source (solve_sources; 0: its own)")
@@ -60,14 +124,7 @@ def main():
     hip = os.path.join(a.out, f"{tag}.hip")
     with open(hip, "w") as f:
         f.write(src)
-    asm = os.path.join(a.out, f"{tag}.s")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--offload-device-only", "-S", "-O3", "-std=c++17",
-           "-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=fast-honor-pragmas",
-           *([] if os.environ.get("WOST_JIT_SLP") == "1" else ["-fno-slp-vectorize"]),
-           "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "dcrmontecarlo_amd", "csrc"), hip, "-o", asm]
-    subprocess.run(cmd, check=True)
-    text = open(asm).read()
-    body = text.split("wost_walk_jit:", 1)[1].split(".Lfunc_end", 1)[0]
+    text, body = assemble(hip)
     hist = collections.Counter()
     n = 0
     for line in body.splitlines():
@@ -77,15 +134,17 @@ def main():
         op = s.split()[0]
         hist[op] += 1
         n += 1
-    meta = {k: re.search(rf"\.{k}:\s+(\d+)", text)
-            for k in ("vgpr_count", "sgpr_count", "lds_size", "vgpr_spill_count", "sgpr_spill_count",
-                      "private_segment_fixed_size")}
-    print(f"{a.scenario}: {n} instructions;", ", ".join(f"{k}={m.group(1)}" for k, m in meta.items() if m))
+    print(f"{a.scenario}: {n} instructions;", ", ".join(f"{k}={v}" for k, v in resources(text).items()))
     for pre in ("v_", "s_", "ds_", "global_", "buffer_", "scratch_"):
         print(f"  {pre}*: {sum(c for o, c in hist.items() if o.startswith(pre))}")
     trans = [o for o in hist if re.match(r"v_(exp|log|rcp|rsq|sqrt|sin|cos)_f32", o)]
     print("  transcendental:", {o: hist[o] for o in trans})
     print("  top:", hist.most_common(25))
+    if a.votes:
+        trips = round_trips(body)
+        print(f"  VALU in loops: {loop_valu(body)}; wave votes through a VGPR: {len(trips)}")
+        for n1, s1, n2, s2 in trips:
+            print(f"    {n1}: {s1}\n    {n2}: {s2}")
     if a.show:
         print(body)
 
