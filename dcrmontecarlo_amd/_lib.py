@@ -151,6 +151,12 @@ def _load():
         "wost_solve_range": (c_int32, [H, POINTER(c_float), c_int64, c_int64, c_int64, c_int64, c_int32, c_float,
                                        c_uint64, POINTER(c_double), POINTER(c_double), POINTER(c_float),
                                        POINTER(c_uint32)]),
+        "wost_solve_range_points": (c_int32, [H, POINTER(c_float), c_int64, POINTER(c_int32), c_int64, c_int64, c_int64,
+                                              c_int64, c_int32, c_float, c_uint64, POINTER(c_double), POINTER(c_double),
+                                              POINTER(c_float), POINTER(c_uint32)]),
+        "wost_kernel_source_point_list": (c_int32, [POINTER(WostProblem), POINTER(WostModel), c_int32,
+                                                    POINTER(POINTER(WostField)), c_int32, c_int32, ctypes.c_char_p,
+                                                    c_int64, POINTER(c_int64)]),
         "wost_comm_unique_id": (c_int32, [POINTER(c_uint8)]),
         "wost_comm_create": (c_int32, [POINTER(c_uint8), c_int32, c_int32, c_int32, POINTER(c_void_p)]),
         "wost_comm_destroy": (None, [c_void_p]),

@@ -192,6 +192,7 @@ struct wost_handle {
     std::vector<int32_t> charge_seg;
     wost::DeviceBuffer<float> d_charges;
     wost::DeviceBuffer<int32_t> d_point_code;   // boundary_code of the query points (WalkArgs::point_code)
+    wost::DeviceBuffer<int32_t> d_point_list;   // the point list of a solve (WalkArgs::point_list)
     bool has_source() const { return fields[wost::SLOT_F].present || !charges.empty(); }
     bool delta = false;
     double sigma_bar = 0.0;
@@ -338,10 +339,11 @@ struct KernelChoice {
     double jit_ms = 0.0;           // host time spent compiling
 };
 KernelVariant kernel_variant(const wost_handle* h, const WalkTraits& t, const KernelShape& ks, bool record,
-                             int n_sources);
+                             int n_sources, bool point_list = false);
 int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* ks);
 JitTry jit_kernel_try(wost_handle* h, const KernelVariant& v, JitTicket* ticket);
-int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, int ns, KernelChoice* kc);
+int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, int ns, KernelChoice* kc,
+                  bool point_list = false);
 
 // ---- wost_solve.cpp ----
 constexpr int64_t kMaxBatchWalks = int64_t(1) << 26;   // 64 Mi walks = 512 MiB of per-walk results
@@ -357,6 +359,11 @@ struct SolveRequest {
     bool multi = false;
     int64_t block_begin = 0, block_end = 0;
     int64_t walk_begin = 0, walk_end = -1;   // (-1: W)
+    // the point list of wost_solve_range_points (null: none): the walk range of these n_ids
+    // points only; every output then has n_ids rows in list order
+    const int32_t* point_ids = nullptr;
+    int64_t n_ids = 0;
+    int64_t rows() const { return point_ids ? n_ids : n_points; }   // point rows of the outputs
 };
 
 // Where its results go on the host (each may be null): rows of 2 * channels + 1 doubles per

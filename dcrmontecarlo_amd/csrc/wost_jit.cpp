@@ -783,9 +783,12 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
     // dirichlet_tree; never for a compiled-in polyline)
     const bool dtree = v.dirichlet_tree && !jit_const_dirichlet(opt, nd);
     if (dtree) o << "#define WOST_DIRICHLET_TREE 1\n";
+    // walk-range batches place their walks through WalkArgs::point_list (KernelVariant::point_list)
+    if (v.point_list) o << "#define WOST_POINT_LIST 1\n";
     o << "// generated by libwost (wost_jit.cpp): walk kernel, " << traits_name(t);
     if (nm >= 2) o << ", " << nm << " models";
     if (dtree) o << ", dirichlet tree";
+    if (v.point_list) o << ", point list";
     o << "\n"
       << "#include \"wost_walk.h\"\n\nnamespace {\nstruct GenFields {\n"
       << "    const float* grid;   // tabulated field values (WOST_FK_GRID) in the program buffer\n"

@@ -130,12 +130,13 @@ JitTry jit_kernel_try(wost_handle* h, const KernelVariant& v, JitTicket* ticket)
 // The field-specialised kernel of that shape for walks with traits `t` that score n_sources
 // sources: the one place that reads the rest of the variant off the handle.
 KernelVariant kernel_variant(const wost_handle* h, const WalkTraits& t, const KernelShape& ks, bool record,
-                             int n_sources) {
+                             int n_sources, bool point_list) {
     return KernelVariant{.traits = t, .record = record, .n_sources = n_sources,
                          .n_wavenumbers = t.delta ? h->n_wavenumbers : 0,   // (0: the kernel without the k2 read)
                          .n_charges = (int)h->charges.size(), .n_models = t.delta ? h->n_models : 0,
                          .block = ks.block, .global_polylines = ks.gpoly,
-                         .tree_stage = ks.stage(), .exact_trig = exact_trig_of(h), .dirichlet_tree = ks.dtree};
+                         .tree_stage = ks.stage(), .exact_trig = exact_trig_of(h), .dirichlet_tree = ks.dtree,
+                         .point_list = point_list};
 }
 
 int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* ks) {
@@ -174,7 +175,8 @@ int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* k
 // The kernel of a solve with the handle's fields: the field-specialised one of
 // first_kernel_shape, staging less of the segment tree while what it stages costs the CU
 // its waves; the precompiled one when that is disabled or could not be built.
-int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, int ns, KernelChoice* kc) {
+int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, int ns, KernelChoice* kc,
+                  bool point_list) {
     *kc = KernelChoice{};
     KernelShape& ks = kc->shape;
     int rc;
@@ -182,8 +184,11 @@ int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, i
     int lds_cap = -1;
     // looks ks up and measures its occupancy
     auto lookup = [&]() -> int {
-        kc->jfn = jit_kernel(h, kernel_variant(h, t, ks, record, n_src), &kc->jit_ms);
+        kc->jfn = jit_kernel(h, kernel_variant(h, t, ks, record, n_src, point_list), &kc->jit_ms);
         if (!kc->jfn) {   // the precompiled kernels run 256-thread workgroups, no staged tree, one channel
+            if (point_list)   // (... and read no point list)
+                return fail(WOST_ERR_UNSUPPORTED, "a point list needs the field-specialised kernel%s%s",
+                            h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
             if (!h->charges.empty())
                 return fail(WOST_ERR_UNSUPPORTED, "point sources need the field-specialised kernel%s%s",
                             h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
@@ -229,7 +234,8 @@ namespace {
 int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources, int32_t n_sources,
                        int32_t n_wavenumbers, int32_t n_charges, char* out, int64_t capacity, int64_t* length,
                        const wost_model* models = nullptr, int32_t n_models = 0, const char* const* opt_names = nullptr,
-                       const double* opt_values = nullptr, int32_t n_options = 0, const int32_t* dtree = nullptr) {
+                       const double* opt_values = nullptr, int32_t n_options = 0, const int32_t* dtree = nullptr,
+                       bool point_list = false) {
     if (!pb || !length) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
     if (n_options < 0 || (n_options > 0 && (!opt_names || !opt_values)))
         return fail(WOST_ERR_INVALID_ARG, "need n_options >= 0 names and values");
@@ -278,7 +284,7 @@ int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources,
     // the first solve's kernel without a device: 256 threads, nothing of the tree staged
     KernelShape ks0;
     ks0.dtree = use_dtree(h);
-    KernelVariant v = kernel_variant(h, t, ks0, false, ns);
+    KernelVariant v = kernel_variant(h, t, ks0, false, ns, point_list);
     // study builds: offline study of the tree kernels' LDS staging (tools/jit_isa.py --stage):
     // the source of staging level WOST_KERNEL_SOURCE_STAGE (2: records and vertices, 1:
     // records, with the tree_lds_block workgroup) instead
@@ -316,6 +322,13 @@ int wost_kernel_source_models(const wost_problem* pb, const wost_model* models, 
                               const wost_field* const* sources, int32_t n_sources, int32_t n_wavenumbers, char* out,
                               int64_t capacity, int64_t* length) {
     return kernel_source_impl(pb, sources, n_sources, n_wavenumbers, 0, out, capacity, length, models, n_models);
+}
+
+int wost_kernel_source_point_list(const wost_problem* pb, const wost_model* models, int32_t n_models,
+                                  const wost_field* const* sources, int32_t n_sources, int32_t n_wavenumbers,
+                                  char* out, int64_t capacity, int64_t* length) {
+    return kernel_source_impl(pb, sources, n_sources, n_wavenumbers, 0, out, capacity, length, models, n_models, nullptr,
+                              nullptr, 0, nullptr, true);
 }
 
 int wost_kernel_source_options(const wost_problem* pb, const char* const* names, const double* values,

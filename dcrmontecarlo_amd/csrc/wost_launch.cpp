@@ -7,14 +7,30 @@
 namespace wost {
 
 int plan_ranges(int64_t n_points, int64_t W, int64_t block_begin, int64_t block_end, int64_t walk_begin,
-                int64_t walk_end, SolveRanges* out, char* msg, size_t msg_cap) {
+                int64_t walk_end, SolveRanges* out, char* msg, size_t msg_cap, const int32_t* point_ids,
+                int64_t n_sel) {
     SolveRanges r;
     r.n_points = n_points;
     r.W = W;
     r.nbpp = (W + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
     const int64_t nb_total = n_points * r.nbpp;
     if (walk_end < 0) walk_end = W;
-    r.range = walk_begin != 0 || walk_end != W;
+    r.range = walk_begin != 0 || walk_end != W || point_ids != nullptr;
+    if (point_ids) {
+        if (n_sel < 1) {
+            std::snprintf(msg, msg_cap, "a point list needs at least one id (got %lld)", (long long)n_sel);
+            return WOST_ERR_INVALID_ARG;
+        }
+        for (int64_t i = 0; i < n_sel; ++i)
+            if (point_ids[i] < 0 || point_ids[i] >= n_points || (i > 0 && point_ids[i] <= point_ids[i - 1])) {
+                std::snprintf(msg, msg_cap,
+                              "point list entry %lld is %d: the ids must be strictly ascending within [0, %lld)",
+                              (long long)i, (int)point_ids[i], (long long)n_points);
+                return WOST_ERR_INVALID_ARG;
+            }
+        r.point_ids = point_ids;
+        r.n_sel = n_sel;
+    }
     if (r.range && (walk_begin < 0 || walk_end <= walk_begin || walk_end > W || walk_begin % WOST_BLOCK_WALKS != 0 ||
                     (walk_end % WOST_BLOCK_WALKS != 0 && walk_end != W))) {
         std::snprintf(msg, msg_cap,
@@ -28,7 +44,7 @@ int plan_ranges(int64_t n_points, int64_t W, int64_t block_begin, int64_t block_
     r.nbr = (r.Wr + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
     if (r.range) {
         block_begin = 0;
-        block_end = n_points * r.nbr;
+        block_end = r.plan_points() * r.nbr;
     } else if (block_begin < 0 || block_end < block_begin || block_end > nb_total) {
         std::snprintf(msg, msg_cap, "block range [%lld,%lld) outside [0,%lld)", (long long)block_begin,
                       (long long)block_end, (long long)nb_total);
@@ -37,7 +53,7 @@ int plan_ranges(int64_t n_points, int64_t W, int64_t block_begin, int64_t block_
     r.block_begin = block_begin;
     r.block_end = block_end;
     r.nblk = block_end - block_begin;
-    r.walks_total = r.nblk == 0 ? 0 : r.range ? n_points * r.Wr : r.blk_end(block_end - 1) - r.blk_begin(block_begin);
+    r.walks_total = r.nblk == 0 ? 0 : r.range ? r.plan_points() * r.Wr : r.blk_end(block_end - 1) - r.blk_begin(block_begin);
     *out = r;
     return WOST_OK;
 }
@@ -53,9 +69,10 @@ bool next_batch(const SolveRanges& r, int64_t j, int64_t batch_limit, Batch* b) 
     b->inv_range_walks = 0.0;
     if (r.range) {
         // whole points' ranges: local walk l is walk walk_begin + l % Wr of point p0 + l / Wr
+        // (with a point list: of the point at list position p0 + l / Wr)
         if (r.Wr > batch_limit) return false;
         const int64_t p0 = j / r.nbr;
-        const int64_t p1 = std::min<int64_t>(r.n_points, p0 + std::max<int64_t>(1, batch_limit / r.Wr));
+        const int64_t p1 = std::min<int64_t>(r.plan_points(), p0 + std::max<int64_t>(1, batch_limit / r.Wr));
         for (int64_t p = p0; p < p1; ++p)
             for (int64_t k = 0; k < r.nbr; ++k) begins.push_back((p - p0) * r.Wr + k * WOST_BLOCK_WALKS);
         count = (p1 - p0) * r.Wr;

@@ -20,6 +20,10 @@ namespace wost {
 // n_points * nbpp blocks of the whole solve, point-major. Walk-range mode (wost_solve_range;
 // walk_begin/walk_end != 0/W): walks [walk_begin, walk_end) of every point; blocks are then
 // (point, block of the range), point-major, and the block range given is ignored.
+// Point list (wost_solve_range_points; point_ids != nullptr): always walk-range mode, [0, W)
+// included, over the n_sel listed points only. The plan's "points" are then list positions:
+// blocks are [n_sel][nbr], point_of() and a batch's p0 / range_point0 index the list, and the
+// kernel (WOST_POINT_LIST) takes the point itself from the list.
 struct SolveRanges {
     int64_t n_points = 0, W = 0;
     int64_t nbpp = 0;                         // blocks per point of the whole solve
@@ -30,6 +34,10 @@ struct SolveRanges {
     int64_t block_begin = 0, block_end = 0;   // resolved (range mode: [0, n_points * nbr))
     int64_t nblk = 0;
     int64_t walks_total = 0;
+    const int32_t* point_ids = nullptr;       // the point list: n_sel strictly ascending ids in [0, n_points)
+    int64_t n_sel = 0;
+    // the points the plan covers: list positions with a list, else every point
+    int64_t plan_points() const { return point_ids ? n_sel : n_points; }
 
     // block -> global walk range (block mode)
     int64_t blk_begin(int64_t j) const { return (j / nbpp) * W + (j % nbpp) * WOST_BLOCK_WALKS; }
@@ -42,9 +50,12 @@ struct SolveRanges {
 };
 
 // Resolves and validates the ranges of a solve of n_points >= 0 points with W >= 1 walks
-// each (walk_end < 0: W). Returns WOST_OK, or WOST_ERR_INVALID_ARG with the message in msg.
+// each (walk_end < 0: W). point_ids: the point list of n_sel ids, or null. Returns WOST_OK,
+// or WOST_ERR_INVALID_ARG with the message in msg (a list that is empty, not strictly
+// ascending or that names a point outside [0, n_points) among them).
 int plan_ranges(int64_t n_points, int64_t W, int64_t block_begin, int64_t block_end, int64_t walk_begin,
-                int64_t walk_end, SolveRanges* out, char* msg, size_t msg_cap);
+                int64_t walk_end, SolveRanges* out, char* msg, size_t msg_cap, const int32_t* point_ids = nullptr,
+                int64_t n_sel = 0);
 
 // One launch's blocks [j, j2) and the WalkArgs fields that place its walks.
 struct Batch {
@@ -58,8 +69,9 @@ struct Batch {
     double inv_range_walks = 0.0;
 };
 
-// The batch that starts at block j: whole blocks (range mode: whole points' ranges) of at
-// most batch_limit walks together. false: block j alone exceeds batch_limit.
+// The batch that starts at block j: whole blocks (range mode: whole points' ranges; with a
+// point list, whole list positions' ranges) of at most batch_limit walks together. false:
+// block j alone exceeds batch_limit.
 bool next_batch(const SolveRanges& r, int64_t j, int64_t batch_limit, Batch* b);
 
 struct LaunchIn {

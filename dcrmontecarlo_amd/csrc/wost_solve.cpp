@@ -74,8 +74,10 @@ int check_request(const wost_handle* h, const SolveRequest& rq, SolveRanges* ran
     if (n_points > 0 && W > (int64_t(1) << 53) / n_points)
         return fail(WOST_ERR_INVALID_ARG, "n_points * nWalks must stay below 2^53 walks");
     char msg[512];
+    if (rq.point_ids && n_points > INT32_MAX)
+        return fail(WOST_ERR_INVALID_ARG, "a point list takes at most 2^31 - 1 query points per solve");
     if (int rc = plan_ranges(n_points, W, rq.block_begin, rq.block_end, rq.walk_begin, rq.walk_end, ranges, msg,
-                             sizeof(msg)))
+                             sizeof(msg), rq.point_ids, rq.n_ids))
         return fail(rc, "%s", msg);
     for (int64_t i = 0; i < 2 * n_points; ++i)
         if (!std::isfinite(points[i])) return fail(WOST_ERR_INVALID_ARG, "solve point %lld is not finite", (long long)(i / 2));
@@ -110,24 +112,27 @@ int check_request(const wost_handle* h, const SolveRequest& rq, SolveRanges* ran
     return WOST_OK;
 }
 
-// Pinned staging: [points | one batch's block ranges | the block sums], 64-byte aligned;
-// the device holds the first two parts in one buffer of the same layout (h->d_points,
-// h->d_begin), so that one copy brings the points and the first batch's block ranges (C2: a
-// copy and its ~6 us gap less)
+// Pinned staging: [points | one batch's block ranges | the block sums | the point list],
+// 64-byte aligned; the device holds the first two parts in one buffer of the same layout
+// (h->d_points, h->d_begin), so that one copy brings the points and the first batch's block
+// ranges (C2: a copy and its ~6 us gap less). The point list (wost_solve_range_points; n_sel
+// ids, 0: none) has a device buffer of its own (h->d_point_list).
 struct Staging {
     float* points = nullptr;
     int64_t* begin = nullptr;
     double* bstats = nullptr;
-    size_t pts_bytes = 0, beg_bytes = 0, bs_bytes = 0;
+    int32_t* ids = nullptr;
+    size_t pts_bytes = 0, beg_bytes = 0, bs_bytes = 0, ids_bytes = 0;
 };
 
-int stage_buffers(wost_handle* h, int64_t n_points, int64_t nblk, int row, Staging* st) {
+int stage_buffers(wost_handle* h, int64_t n_points, int64_t nblk, int row, int64_t n_sel, Staging* st) {
     auto al64 = [](size_t b) { return (b + 63) / 64 * 64; };
     st->pts_bytes = al64(sizeof(float2) * (size_t)std::max<int64_t>(n_points, 1));
     st->beg_bytes = al64(sizeof(int64_t) * (size_t)(nblk + 1));
     st->bs_bytes = al64(sizeof(double) * (size_t)(kLstatsWords + row * nblk));
+    st->ids_bytes = al64(sizeof(int32_t) * (size_t)std::max<int64_t>(n_sel, 0));
     const size_t dev_bytes = st->pts_bytes + st->beg_bytes;
-    if (int rc = ensure_pin(h, dev_bytes + st->bs_bytes)) return rc;
+    if (int rc = ensure_pin(h, dev_bytes + st->bs_bytes + st->ids_bytes)) return rc;
     if (int rc = ensure_cap(h->d_stage, (int64_t)dev_bytes)) return rc;
     char* const dev = h->d_stage;
     char* const pin = h->h_pin;
@@ -136,6 +141,7 @@ int stage_buffers(wost_handle* h, int64_t n_points, int64_t nblk, int row, Stagi
     st->points = reinterpret_cast<float*>(pin);
     st->begin = reinterpret_cast<int64_t*>(pin + st->pts_bytes);
     st->bstats = reinterpret_cast<double*>(pin + dev_bytes);
+    st->ids = reinterpret_cast<int32_t*>(pin + dev_bytes + st->bs_bytes);
     return WOST_OK;
 }
 
@@ -380,6 +386,7 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
     const int ns = h->channels();
     const int row = 2 * ns + 1;   // doubles per block / point row
     const int64_t n_points = rq.n_points;
+    const bool listed = rq.point_ids != nullptr;   // (R.plan_points() rows then: list order)
     const WalkTraits t = walk_traits(h);
 
     HIP_TRY(hipSetDevice(h->device));
@@ -392,7 +399,8 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
                                           "charge in its ball: there is no sample point)");
 
     h->timing = wost_timing{};
-    if (out.point_stats) std::fill(out.point_stats, out.point_stats + row * n_points, 0.0);
+    if (out.records && listed) return fail(WOST_ERR_UNSUPPORTED, "wost_solve_history takes no point list");
+    if (out.point_stats) std::fill(out.point_stats, out.point_stats + row * rq.rows(), 0.0);
     if (R.nblk == 0) return WOST_OK;
 
     // walks per launch: the recorder's device buffer bounds it
@@ -411,8 +419,13 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
                     (long long)R.Wr, (long long)batch_limit);
 
     Staging st;
-    if ((rc = stage_buffers(h, n_points, R.nblk, row, &st)) != WOST_OK) return rc;
+    if ((rc = stage_buffers(h, n_points, R.nblk, row, listed ? R.n_sel : 0, &st)) != WOST_OK) return rc;
     std::memcpy(st.points, rq.points, sizeof(float2) * (size_t)n_points);
+    if (listed) {   // the point list, through the staging (its copy is done when the solve's last wait is)
+        if ((rc = ensure_cap(h->d_point_list, R.n_sel)) != WOST_OK) return rc;
+        std::memcpy(st.ids, rq.point_ids, sizeof(int32_t) * (size_t)R.n_sel);
+        HIP_TRY(hipMemcpyAsync(h->d_point_list, st.ids, sizeof(int32_t) * (size_t)R.n_sel, hipMemcpyHostToDevice, h->stream));
+    }
     // the points go with the first batch's block ranges, unless the query points' alpha
     // (delta tracking) needs them first
     bool points_pending = true;
@@ -430,9 +443,10 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
         HIP_TRY(d_rec.reserve((size_t)(std::min<int64_t>(R.walks_total, batch_limit) * rec_stride * kRecFloats)));
 
     KernelChoice kc;
-    if ((rc = choose_kernel(h, t, out.records != nullptr, n_src, ns, &kc)) != WOST_OK) return rc;
+    if ((rc = choose_kernel(h, t, out.records != nullptr, n_src, ns, &kc, listed)) != WOST_OK) return rc;
     const int block = kc.shape.block;
     WalkArgs a = fill_walk_args(h, rq, t, kc, d_rec);
+    if (listed) a.point_list = h->d_point_list;
     if ((rc = setup_pools(h, t, n_src, kc.blocks_per_cu, &a)) != WOST_OK) return rc;
     if ((rc = launch_point_alpha_for(h, t, kc.jfn, n_points, &a)) != WOST_OK) return rc;
     if ((rc = setup_point_sources(h, t, rq, &a)) != WOST_OK) return rc;

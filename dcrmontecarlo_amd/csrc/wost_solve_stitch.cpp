@@ -42,7 +42,8 @@ void add_timing(wost_timing& acc, const wost_timing& t) {
     acc.precompiled_walks += t.precompiled_walks;
 }
 
-// A solve of walks [w_begin, w_begin + Wr) of every point that takes several solves of
+// A solve of walks [w_begin, w_begin + Wr) of every point (with a point list: of every listed
+// point, one row each) that takes several solves of
 // block-aligned sub-ranges (wost_solve_range beyond one launch per point, solve_race): each
 // piece's block rows, values and steps are scattered into the whole range's layout, so the
 // block sums, their order and every output are those of one solve.
@@ -59,13 +60,13 @@ struct Stitch {
 
     Stitch(const SolveRequest& whole, const SolveOutputs& o, int ns_, int64_t w0, int64_t w1)
         : rq(whole), out(o), ns(ns_), w_begin(w0), Wr(w1 - w0), nbr((w1 - w0 + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS),
-          all((size_t)whole.n_points * nbr * (2 * ns_ + 1)) {}
+          all((size_t)whole.rows() * nbr * (2 * ns_ + 1)) {}
 };
 
 // Solves walks [c0, c1) of every point into the stitched solve's outputs and timing.
 int solve_piece(wost_handle* h, Stitch& s, int64_t c0, int64_t c1) {
     const int row = 2 * s.ns + 1;
-    const int64_t n_points = s.rq.n_points;
+    const int64_t n_points = s.rq.rows();   // (point rows of the outputs)
     const int64_t wc = c1 - c0, nbc = (wc + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS;
     const int64_t woff = c0 - s.w_begin, boff = woff / WOST_BLOCK_WALKS;
     s.part.resize((size_t)n_points * nbc * row);
@@ -99,8 +100,8 @@ void stitched_stats(const Stitch& s) {
     const int row = 2 * s.ns + 1;
     if (s.out.block_stats) std::memcpy(s.out.block_stats, s.all.data(), sizeof(double) * s.all.size());
     if (!s.out.point_stats) return;
-    std::fill(s.out.point_stats, s.out.point_stats + (size_t)row * s.rq.n_points, 0.0);
-    for (int64_t p = 0; p < s.rq.n_points; ++p)
+    std::fill(s.out.point_stats, s.out.point_stats + (size_t)row * s.rq.rows(), 0.0);
+    for (int64_t p = 0; p < s.rq.rows(); ++p)
         for (int64_t k = 0; k < s.nbr; ++k)
             for (int c = 0; c < row; ++c) s.out.point_stats[(size_t)row * p + c] += s.all[((size_t)p * s.nbr + k) * row + c];
 }
@@ -210,14 +211,26 @@ int wost_solve(wost_handle* h, const float* points, int64_t n_points, int64_t W,
 int wost_solve_range(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t walk_begin,
                      int64_t walk_end, int32_t max_steps, float eps, uint64_t seed, double* block_stats,
                      double* point_stats, float* walk_values, uint32_t* walk_steps) {
+    return wost_solve_range_points(h, points, n_points, nullptr, 0, W, walk_begin, walk_end, max_steps, eps, seed,
+                                   block_stats, point_stats, walk_values, walk_steps);
+}
+
+int wost_solve_range_points(wost_handle* h, const float* points, int64_t n_points, const int32_t* point_ids,
+                            int64_t n_ids, int64_t W, int64_t walk_begin, int64_t walk_end, int32_t max_steps,
+                            float eps, uint64_t seed, double* block_stats, double* point_stats, float* walk_values,
+                            uint32_t* walk_steps) {
     if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
     SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
     rq.multi = true;
+    rq.point_ids = point_ids;   // (null: every point, wost_solve_range)
+    rq.n_ids = point_ids ? n_ids : 0;
     const SolveOutputs out = outputs(block_stats, point_stats, walk_values, walk_steps);
-    if (walk_begin == 0 && walk_end == W) return solve_impl(h, rq, out);   // the whole range: an ordinary solve
+    // the whole range of every point: an ordinary solve (of a list: a range all the same)
+    if (walk_begin == 0 && walk_end == W && !point_ids) return solve_impl(h, rq, out);
     const int ns = h->channels();
     const int64_t chunk = (kMaxBatchWalks / ns) / WOST_BLOCK_WALKS * WOST_BLOCK_WALKS;   // walks of a point per launch
-    if (walk_end - walk_begin <= chunk || walk_begin < 0 || walk_end <= walk_begin || n_points <= 0) {
+    if (walk_end - walk_begin <= chunk || walk_begin < 0 || walk_end <= walk_begin || n_points <= 0 ||
+        (point_ids && n_ids < 1)) {
         rq.block_end = 0;   // (a range names its walks only)
         rq.walk_begin = walk_begin;
         rq.walk_end = walk_end;

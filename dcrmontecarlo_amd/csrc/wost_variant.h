@@ -49,6 +49,8 @@ struct KernelVariant {
     bool exact_trig = true;          // wost_set_trig: correctly rounded directions
     bool dirichlet_tree = false;     // the Dirichlet distance through the Dirichlet polyline's segment tree
                                      // (poly_distance_tree; records and vertices through L1/L2, nothing staged)
+    bool point_list = false;         // walk-range batches take their points from WalkArgs::point_list
+                                     // (WOST_POINT_LIST; wost_solve_range_points)
 };
 
 inline bool operator==(const KernelVariant& a, const KernelVariant& b) {
@@ -56,7 +58,7 @@ inline bool operator==(const KernelVariant& a, const KernelVariant& b) {
            a.n_wavenumbers == b.n_wavenumbers && a.n_charges == b.n_charges && a.n_models == b.n_models &&
            a.block == b.block &&
            a.global_polylines == b.global_polylines && a.tree_stage == b.tree_stage && a.exact_trig == b.exact_trig &&
-           a.dirichlet_tree == b.dirichlet_tree;
+           a.dirichlet_tree == b.dirichlet_tree && a.point_list == b.point_list;
 }
 
 }  // namespace wost

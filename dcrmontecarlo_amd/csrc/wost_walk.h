@@ -121,6 +121,16 @@ struct WalkArgs {
     int32_t dtree_depth;
     int32_t dtree_leaf;
     float dtree_kmax;
+    // point list (wost_solve_range_points; read only by kernels built with WOST_POINT_LIST, in
+    // walk-range batches): the n_sel ascending ids of the points solved. range_point0 and the
+    // quotient l / range_walks then index this list, and the walk's point -- its id, its
+    // Philox stream, its entry of points, point_alpha and point_code, all full-size arrays --
+    // is point_list[range_point0 + l / range_walks]. Outputs stay indexed by the local walk.
+    // Every launch can carry the list: the walk pools keep running with it (a parked walk
+    // holds its own id and state, never its point), and so would the recorder (indexed by the
+    // local walk), though no entry point records a list solve (solve_impl refuses). Null
+    // otherwise.
+    const int32_t* point_list;
 };
 
 // The Dirichlet polyline's tree as poly_distance_tree reads it (records and vertices through
@@ -164,8 +174,20 @@ __device__ __forceinline__ int charge_int(const float* c, int i) {
 // kernels; expanded in place their code is instruction for instruction what it was.
 // WOST_WALK_ID_CORRECTED(path, dir): the host check's counter of the corrections that fire
 // (path 0 range, 1 small32, 2 64-bit; dir -1 / +1); nothing in the kernels.
+// WOST_POINT_LIST (default 0; wost_jit.cpp defines it for a KernelVariant with point_list): a
+// fourth way to place a walk -- the range path's quotient indexes WalkArgs::point_list, and
+// the list's entry is the point. Compile-time for the reason above: a data-driven branch on
+// the list pointer in every kernel would change the kernels that never see a list.
 #ifndef WOST_WALK_ID_CORRECTED
 #define WOST_WALK_ID_CORRECTED(path, dir)
+#endif
+#ifndef WOST_POINT_LIST
+#define WOST_POINT_LIST 0
+#endif
+#if WOST_POINT_LIST
+#define WOST_RANGE_POINT(A, q) ((uint64_t)(uint32_t)A.point_list[(uint64_t)A.range_point0 + q])
+#else
+#define WOST_RANGE_POINT(A, q) ((uint64_t)A.range_point0 + q)
 #endif
 #define WOST_WALK_OF_LOCAL(A, lid, wid, pid) \
     if (A.range_walks > 0) { \
@@ -174,7 +196,7 @@ __device__ __forceinline__ int charge_int(const float* c, int i) {
         int32_t rem = (int32_t)(l32 - q * rw); \
         if (rem < 0) { --q; rem += (int32_t)rw; WOST_WALK_ID_CORRECTED(0, -1) } \
         else if (rem >= (int32_t)rw) { ++q; rem -= (int32_t)rw; WOST_WALK_ID_CORRECTED(0, +1) } \
-        pid = (uint64_t)A.range_point0 + q; \
+        pid = WOST_RANGE_POINT(A, q); \
         wid = pid * (uint64_t)A.walks_per_point + (uint64_t)A.range_offset + (uint64_t)rem; \
     } else if (A.small32) { \
         const uint32_t local = A.base_off + (uint32_t)lid, w32 = (uint32_t)A.walks_per_point; \

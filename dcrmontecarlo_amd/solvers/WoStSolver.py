@@ -91,6 +91,97 @@ def stats_from_sums(sums: np.ndarray, n_walks: int, total_steps=None, kernel_ms=
                       kernel_ms=float(kernel_ms), total_ms=float(total_ms))
 
 
+@dataclass
+class ToleranceStats:
+    """What solve_to_tolerance ran and found, per point (C channels: ``mean`` and ``stderr``
+    are [N] when C == 1, else [C, N])."""
+
+    walks: np.ndarray       # [N] int64: n_p, the walks point p ran (a checkpoint of the schedule)
+    mean: np.ndarray        # float64: sum / n_p
+    stderr: np.ndarray      # float64: sample std / sqrt(n_p)
+    converged: np.ndarray   # [N] bool: every channel met the tolerance at n_p (else n_p == max_walks)
+    sums: np.ndarray        # [N, 2C+1] float64: wost_solve_range(0, n_p)'s point row (sum, sum^2 per channel, steps)
+    rounds: int             # launches of the point-list kernel's solve
+    total_walks: int        # sum of n_p
+    total_steps: int
+    kernel_ms: float        # walk-kernel time summed over the rounds (HIP events)
+    total_ms: float         # device time summed over the rounds
+
+
+def tolerance_schedule(min_walks: int, max_walks: int) -> list:
+    """The checkpoints n_0 < n_1 < ... = max_walks of solve_to_tolerance: n_0 is min_walks
+    rounded up to whole blocks (WOST_BLOCK_WALKS) and capped at max_walks, then each is twice
+    the one before, capped at max_walks. Every end but the last is block-aligned."""
+    min_walks, max_walks = int(min_walks), int(max_walks)
+    if min_walks < 1 or max_walks < 1:
+        raise ValueError("min_walks and max_walks must be >= 1")
+    B = _lib.WOST_BLOCK_WALKS
+    ends = [min(-(-min_walks // B) * B, max_walks)]
+    while ends[-1] < max_walks:
+        ends.append(min(2 * ends[-1], max_walks))
+    return ends
+
+
+def tolerance_rule(sums: np.ndarray, n_walks, rel_tol: float, abs_tol: float):
+    """The stopping rule on running point rows ``sums`` [P, 2C+1] after ``n_walks`` walks
+    (a number or [P]): (mean [C, P], stderr [C, P], converged [P]). Mean and standard error are
+    stats_from_sums's. A channel has converged when stderr <= max(abs_tol, rel_tol * |mean|)
+    and, unless abs_tol > 0, its sum of squares is > 0: walks that all scored an exact 0 say
+    nothing about a relative error. A NaN never converges. A point has converged when every
+    channel has."""
+    sums = np.asarray(sums, np.float64)
+    C = (sums.shape[1] - 1) // 2
+    n = np.broadcast_to(np.asarray(n_walks, np.float64), (sums.shape[0],))
+    s, q = sums[:, 0:2 * C:2].T, sums[:, 1:2 * C:2].T
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        mean = s / n
+        var = np.maximum(q / n - mean * mean, 0.0) * (n / np.maximum(n - 1, 1))
+        se = np.sqrt(var / n)
+        ok = (se <= np.maximum(abs_tol, rel_tol * np.abs(mean))) & ((q > 0.0) | (abs_tol > 0.0))
+    ok &= np.isfinite(se) & np.isfinite(mean)
+    return mean, se, ok.all(axis=0)
+
+
+def run_to_tolerance(run_round, n_points: int, n_channels: int, *, rel_tol: float = 0.0, abs_tol: float = 0.0,
+                     min_walks: int = 16384, max_walks: int):
+    """The rounds of solve_to_tolerance as a pure function of numpy arrays.
+    ``run_round(ids, walk_begin, walk_end)`` returns the block rows [len(ids), blocks, 2C+1]
+    of walks [walk_begin, walk_end) of the points ``ids`` (ascending int32), in block order.
+    Round 0 runs [0, n_0) of every point, round k [n_{k-1}, n_k) of the points still active
+    (tolerance_schedule); after a round a point's running row is its previous row plus the
+    round's block rows, added one block at a time in block order (the order in which
+    wost_solve_range sums a point's row), and tolerance_rule decides which points stop. A
+    stopped point is never run again. Returns (sums [N, 2C+1], walks [N] int64, converged [N]
+    bool, rounds)."""
+    rel_tol, abs_tol = float(rel_tol), float(abs_tol)
+    if not (rel_tol >= 0.0 and abs_tol >= 0.0):
+        raise ValueError("rel_tol and abs_tol must be >= 0")
+    N, row = int(n_points), 2 * int(n_channels) + 1
+    sums = np.zeros((N, row), np.float64)
+    walks = np.zeros(N, np.int64)
+    converged = np.zeros(N, bool)
+    active = np.arange(N, dtype=np.int32)
+    begin, rounds = 0, 0
+    for end in tolerance_schedule(min_walks, max_walks):
+        if active.size == 0:
+            break
+        blocks = np.asarray(run_round(active.copy(), begin, end), np.float64)
+        nbr = -(-(end - begin) // _lib.WOST_BLOCK_WALKS)
+        if blocks.shape != (active.size, nbr, row):
+            raise ValueError(f"run_round returned {blocks.shape}, expected {(active.size, nbr, row)}")
+        acc = sums[active]
+        for k in range(nbr):
+            acc = acc + blocks[:, k, :]
+        sums[active] = acc
+        walks[active] = end
+        rounds += 1
+        done = tolerance_rule(acc, end, rel_tol, abs_tol)[2]
+        converged[active] = done
+        active = active[~done]
+        begin = end
+    return sums, walks, converged, rounds
+
+
 def _problem(dxy, nxy, g, f, sigma, alpha, compat, device, sigma_bar):
     """wost_problem for the given geometry and fields (None = absent; the library
     applies the sigma = 0 / alpha = 1 defaults itself) and the objects to keep alive."""
@@ -110,7 +201,7 @@ def _problem(dxy, nxy, g, f, sigma, alpha, compat, device, sigma_bar):
 def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoundary=None, source=None,
                   sigma=None, alpha=None, *, sigma_bar: float | None = None, compat: str = "reference",
                   sources=None, n_wavenumbers: int = 0, models=None, options: dict | None = None,
-                  dirichlet_tree: int | None = None, dirichlet_tree_leaf: int = 0) -> str:
+                  dirichlet_tree: int | None = None, dirichlet_tree_leaf: int = 0, point_list: bool = False) -> str:
     """HIP source of the field-specialised walk kernel a WostSolver_2D with these
     arguments would compile (no device needed; wost_kernel_source). sources: the fields
     of a multi-source solve (solve_sources; wost_kernel_source_sources); n_wavenumbers: the
@@ -120,7 +211,12 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
     (wost_kernel_source_options; the plain single-source kernel only); dirichlet_tree: the
     min_segments of set_dirichlet_tree called first (0 forces the Dirichlet tree, -1 forbids
     it, None: the default threshold; wost_kernel_source_dirichlet_tree, the plain
-    single-source kernel only), dirichlet_tree_leaf its leaf_segments."""
+    single-source kernel only), dirichlet_tree_leaf its leaf_segments; point_list: the kernel
+    a solve with a point list launches (solve_range(point_ids=...), solve_to_tolerance;
+    wost_kernel_source_point_list; with sources, wavenumbers and models, not with options or
+    dirichlet_tree)."""
+    if point_list and (options or dirichlet_tree is not None):
+        raise ValueError("point_list: not together with options or dirichlet_tree")
     if options and (sources or n_wavenumbers or models is not None):
         raise ValueError("options: only with the problem's own source, no wavenumbers and no models")
     if dirichlet_tree is not None and (options or sources or n_wavenumbers or models is not None):
@@ -155,6 +251,10 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
         call = lambda buf, cap: _lib.lib.wost_kernel_source_models(ctypes.byref(prob), marr, len(models), arr,
                                                                     len(packed), int(n_wavenumbers), buf, cap,
                                                                     ctypes.byref(n))
+    if point_list:
+        marr, nm = (None, 0) if models is None else (marr, len(models))
+        call = lambda buf, cap: _lib.lib.wost_kernel_source_point_list(ctypes.byref(prob), marr, nm, arr, len(packed),
+                                                                        int(n_wavenumbers), buf, cap, ctypes.byref(n))
     if options:
         names = (ctypes.c_char_p * len(options))(*[k.encode() for k in options])
         values = (ctypes.c_double * len(options))(*[float(v) for v in options.values()])
@@ -373,22 +473,100 @@ class WostSolver_2D:
         return bs
 
     def solve_range(self, solvePoints, nWalks: int, walk_begin: int, walk_end: int, maxSteps: int = 1000,
-                    eps: float = 1e-4, seed: int = 0):
+                    eps: float = 1e-4, seed: int = 0, point_ids=None, walk_values: np.ndarray | None = None,
+                    walk_steps: np.ndarray | None = None):
         """Walks [walk_begin, walk_end) of every point (block-aligned ends; wost_solve_range):
         the (sum, sum^2, steps) rows of its blocks, [N, blocks, 3] ([N, blocks, 2C+1] with C
         channels: sources x wavenumbers), each equal to the
-        corresponding block of the full solve. The unit of dcrmontecarlo_amd.comm's sharding."""
+        corresponding block of the full solve. The unit of dcrmontecarlo_amd.comm's sharding.
+
+        point_ids (wost_solve_range_points): strictly ascending indices into ``solvePoints``;
+        only these points are walked, with the ids -- and so the random streams and the bits
+        -- they have in the solve of all points. The result then has len(point_ids) rows in
+        list order, row r bitwise row point_ids[r] of the call without a list. Needs the
+        field-specialised kernel (NotImplementedError after set_jit(False)); a bad list raises
+        ValueError. walk_values / walk_steps: optional float32 [rows, walk_end - walk_begin, C]
+        / uint32 [rows, walk_end - walk_begin] arrays that receive the per-walk results."""
         p = _points_np(solvePoints)
         n = p.shape[0]
+        ids = None
+        if point_ids is not None:
+            ids = np.ascontiguousarray(np.asarray(_np(point_ids)).ravel())
+            if ids.size == 0:
+                raise ValueError("point_ids must hold at least one point")
+            if (not np.issubdtype(ids.dtype, np.integer) or ids.min() < -2**31 or ids.max() >= 2**31):
+                raise ValueError("point_ids must be integers that fit 32 bits")
+            ids = ids.astype(np.int32)
+        rows = n if ids is None else ids.shape[0]
         nbr = -(-(int(walk_end) - int(walk_begin)) // _lib.WOST_BLOCK_WALKS)
         ns = ctypes.c_int32(1)   # values per walk: sources x wavenumbers
         _lib.check(_lib.lib.wost_num_channels(self._h, ctypes.byref(ns)), "wost_num_channels")
-        bs = np.zeros((n, max(nbr, 0), 2 * ns.value + 1), np.float64)
-        _lib.check(_lib.lib.wost_solve_range(self._h, _lib.fptr(p), n, int(nWalks), int(walk_begin), int(walk_end),
-                                             int(maxSteps), float(eps), int(seed) & (2**64 - 1), _lib.dptr(bs), None,
-                                             None, None), "WostSolver_2D.solve_range")
+        for a, dt, size in ((walk_values, np.float32, ns.value), (walk_steps, np.uint32, 1)):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or
+                                  a.size != rows * max(int(walk_end) - int(walk_begin), 0) * size):
+                raise ValueError("walk_values / walk_steps: contiguous float32 [rows, walks, C] / uint32 [rows, walks]")
+        bs = np.zeros((rows, max(nbr, 0), 2 * ns.value + 1), np.float64)
+        if ids is None:
+            rc = _lib.lib.wost_solve_range(self._h, _lib.fptr(p), n, int(nWalks), int(walk_begin), int(walk_end),
+                                           int(maxSteps), float(eps), int(seed) & (2**64 - 1), _lib.dptr(bs), None,
+                                           _lib.fptr(walk_values), _lib.u32ptr(walk_steps))
+        else:
+            rc = _lib.lib.wost_solve_range_points(self._h, _lib.fptr(p), n, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                  rows, int(nWalks), int(walk_begin), int(walk_end), int(maxSteps),
+                                                  float(eps), int(seed) & (2**64 - 1), _lib.dptr(bs), None,
+                                                  _lib.fptr(walk_values), _lib.u32ptr(walk_steps))
+        _lib.check(rc, "WostSolver_2D.solve_range")
         self.last_timing = self.timing()
         return bs
+
+    def solve_to_tolerance(self, solvePoints, *, rel_tol: float = 0.0, abs_tol: float = 0.0, min_walks: int = 16384,
+                           max_walks: int, maxSteps: int = 1000, eps: float = 1e-4, seed: int = 0):
+        """Solve each point to a target standard error instead of a fixed walk count: a point
+        stops once stderr <= max(abs_tol, rel_tol * |mean|) in every channel, or at
+        ``max_walks``. Walks run in rounds over the points still unconverged only (DESIGN.md
+        7d): round 0 walks [0, n_0) of every point, n_0 = ``min_walks`` rounded up to whole
+        blocks; round k walks [n_{k-1}, min(2 n_{k-1}, max_walks)). Every round launches the
+        point-list kernel (solve_range(point_ids=...)), so the points keep their ids.
+
+        The result is a prefix of the fixed solve: point p, stopped after n_p walks, holds bit
+        for bit the sums of walks [0, n_p) of ``solve(..., nWalks=max_walks)`` -- with both
+        tolerances 0 every point runs to ``max_walks`` and ``u`` is that solve's. It scores
+        whatever channels are installed on the handle (inside sources_installed,
+        point_sources_installed, models_installed, with set_wavenumbers).
+
+        Stopping on an estimated error, looked at only at the doubling checkpoints, biases the
+        estimate slightly: a point whose early walks happen to agree stops early, and the
+        standard error it reports is the one that let it stop. ``min_walks`` is the guard --
+        no point is judged on fewer walks. A channel whose walks all scored an exact 0 is not
+        taken as converged to a relative tolerance (only with abs_tol > 0); NaN never converges.
+
+        Returns ``(u, stats)``: u float32 [N, 1] ([C, N] with C > 1 channels; a torch tensor if
+        the points were one) and a :class:`ToleranceStats`. Needs the field-specialised kernel."""
+        p = _points_np(solvePoints)
+        n = p.shape[0]
+        C = self.num_channels()
+        acc = {"steps": 0, "kernel_ms": 0.0, "total_ms": 0.0}
+
+        def run_round(ids, w0, w1):
+            bs = self.solve_range(p, int(max_walks), w0, w1, maxSteps, eps, seed, point_ids=ids)
+            t = self.last_timing
+            acc["steps"] += int(t["total_steps"])
+            acc["kernel_ms"] += float(t["walk_kernel_ms"])
+            acc["total_ms"] += float(t["total_ms"])
+            return bs
+
+        sums, walks, converged, rounds = run_to_tolerance(run_round, n, C, rel_tol=rel_tol, abs_tol=abs_tol,
+                                                          min_walks=min_walks, max_walks=max_walks)
+        mean, se, _ = tolerance_rule(sums, np.maximum(walks, 1), rel_tol, abs_tol)
+        self.last_point_sums = sums
+        if C == 1:
+            mean, se = mean[0], se[0]
+            u = _like(mean.astype(np.float32).reshape(n, 1), solvePoints)
+        else:
+            u = mean.astype(np.float32)
+        return u, ToleranceStats(walks=walks, mean=mean, stderr=se, converged=converged, sums=sums, rounds=rounds,
+                                 total_walks=int(walks.sum()), total_steps=acc["steps"], kernel_ms=acc["kernel_ms"],
+                                 total_ms=acc["total_ms"])
 
     def set_jit(self, enable: bool):
         """Use the field-specialised (hiprtc) walk kernel (default) or the precompiled

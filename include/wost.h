@@ -429,6 +429,27 @@ int wost_solve_range(wost_handle* h, const float* points, int64_t n_points,
                      double* block_stats, double* point_stats,
                      float* walk_values, uint32_t* walk_steps);
 
+/* wost_solve_range over a subset of the points (no reference counterpart):
+ * walks [walk_begin, walk_end) of the n_ids points point_ids[r] only, which keep their
+ * true ids -- and so their Philox streams, block sums and point data -- of the solve of all
+ * n_points points. wost_solve_range's contract, with every output in n_ids rows in list
+ * order instead of n_points rows: row r is bit for bit row point_ids[r] of wost_solve_range
+ * with the same other arguments, for any channel count (sources, wavenumbers, models, point
+ * charges). `points` stays the full array of n_points points. point_ids == NULL (n_ids is
+ * then ignored) is wost_solve_range itself.
+ * WOST_ERR_INVALID_ARG when n_ids < 1, or the ids are not strictly ascending within
+ * [0, n_points). The list is read by a field-specialised kernel of its own (one more compile
+ * per problem, which the solve waits for: it never starts on the precompiled kernel
+ * meanwhile); WOST_ERR_UNSUPPORTED at the solve when that kernel is disabled (wost_set_jit)
+ * or cannot be built. The segment-tree kernels keep their walk pools with a list. Other
+ * solves of the handle are unaffected: a wost_solve_range afterwards gives its usual bits. */
+int wost_solve_range_points(wost_handle* h, const float* points, int64_t n_points,
+                            const int32_t* point_ids, int64_t n_ids,
+                            int64_t walks_per_point, int64_t walk_begin, int64_t walk_end,
+                            int32_t max_steps, float eps, uint64_t seed,
+                            double* block_stats, double* point_stats,
+                            float* walk_values, uint32_t* walk_steps);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, RCCL over xGMI. The reference
  * has no parallel code; walks shard trivially, and the only exchange is one
@@ -657,6 +678,13 @@ int wost_kernel_source_channels(const wost_problem* problem, const wost_field* c
 int wost_kernel_source_models(const wost_problem* problem, const wost_model* models, int32_t n_models,
                               const wost_field* const* sources, int32_t n_sources, int32_t n_wavenumbers,
                               char* out, int64_t capacity, int64_t* length);
+
+/* wost_kernel_source_models' kernel as wost_solve_range_points launches it: walk-range
+ * batches take their points from a point list (WOST_POINT_LIST; n_models 0 and models NULL:
+ * wost_kernel_source_channels' kernel). Nothing else of the source differs. Host only. */
+int wost_kernel_source_point_list(const wost_problem* problem, const wost_model* models, int32_t n_models,
+                                  const wost_field* const* sources, int32_t n_sources, int32_t n_wavenumbers,
+                                  char* out, int64_t capacity, int64_t* length);
 
 /* The same for a handle with n_charges point charges in n_sources source channels
  * (wost_set_point_sources; the problem must have no source field) and n_wavenumbers

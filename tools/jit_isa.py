@@ -6,7 +6,8 @@ compiles it with hipcc for gfx950 with hiprtc's options, and prints the
 kernel's resource usage and an instruction histogram (static counts).
 Usage: python tools/jit_isa.py dcr_dipole [--out build/jit] [--show] [--votes] [--wavenumbers NK] [--sources NS]
        [--point-charges PC]   (point sources: PC charges in NS sources, compat="fixed")
-       [--models M]           (set_models: the scenario's fields, a constant background, then perturbed copies)"""
+       [--models M]           (set_models: the scenario's fields, a constant background, then perturbed copies)
+       [--point-list]         (the kernel of solve_range(point_ids=...) / solve_to_tolerance: WOST_POINT_LIST)"""
 import argparse
 import collections
 import os
@@ -95,7 +96,11 @@ def main():
     ap.add_argument("--models", type=int, default=0,
                     help="NM: conductivity models per walk (set_models; 0: none): the scenario's own fields, a "
                          "constant-alpha background, then copies with a scaled conductivity")
+    ap.add_argument("--point-list", action="store_true",
+                    help="the point-list kernel (solve_range(point_ids=...), solve_to_tolerance); not with --point-charges")
     a = ap.parse_args()
+    if a.point_list and a.point_charges:
+        ap.error("--point-list: not together with --point-charges")
     if a.waves:
         os.environ["WOST_JIT_WAVES"] = a.waves
     from dcrmontecarlo_amd import scenarios as S
@@ -117,10 +122,11 @@ def main():
     else:
         src = sc.kernel_source(n_wavenumbers=a.wavenumbers, **({"sources": [sc.f * (1.0 + k) for k in range(a.sources)]}
                                                                if a.sources else {}),
-                               **({"models": models} if models else {}))
+                               **({"models": models} if models else {}), point_list=a.point_list)
     os.makedirs(a.out, exist_ok=True)
     tag = a.scenario + (f"_nk{a.wavenumbers}" if a.wavenumbers else "") + (f"_ns{a.sources}" if a.sources else "") + (
-        f"_pc{a.point_charges}" if a.point_charges else "") + (f"_nm{a.models}" if a.models else "")
+        f"_pc{a.point_charges}" if a.point_charges else "") + (f"_nm{a.models}" if a.models else "") + (
+        "_list" if a.point_list else "")
     hip = os.path.join(a.out, f"{tag}.hip")
     with open(hip, "w") as f:
         f.write(src)
