@@ -154,6 +154,12 @@ def _load():
         "wost_solve_range_points": (c_int32, [H, POINTER(c_float), c_int64, POINTER(c_int32), c_int64, c_int64, c_int64,
                                               c_int64, c_int32, c_float, c_uint64, POINTER(c_double), POINTER(c_double),
                                               POINTER(c_float), POINTER(c_uint32)]),
+        "wost_solve_range_combined": (c_int32, [H, POINTER(c_float), c_int64, POINTER(c_int32), c_int64, c_int64, c_int64,
+                                                c_int64, c_int32, c_float, c_uint64, POINTER(c_double), c_int32,
+                                                POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
+        "wost_combine_blocks_host": (c_int32, [POINTER(c_float), POINTER(c_int64), c_int64, c_int32, POINTER(c_double),
+                                               c_int32, POINTER(c_double)]),
+        "wost_last_combine_ms": (c_int32, [H, POINTER(c_double)]),
         "wost_kernel_source_point_list": (c_int32, [POINTER(WostProblem), POINTER(WostModel), c_int32,
                                                     POINTER(POINTER(WostField)), c_int32, c_int32, ctypes.c_char_p,
                                                     c_int64, POINTER(c_int64)]),

@@ -7,6 +7,7 @@
 //   wost_solve.cpp          the per-solve steps and solve_impl
 //   wost_solve_stitch.cpp   the wost_solve* entry points, the stitched and raced solves
 //   wost_point_sources.cpp  point-source geometry and setters
+//   wost_combine.cpp        weighted channel combinations on the host (wost_combine.h; no HIP)
 //   wost_api.hip            create / destroy, the setters, the stand-alone device queries
 #pragma once
 
@@ -238,7 +239,7 @@ struct wost_handle {
     wost::DeviceBuffer<float> d_dtree;
 
     hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {};
+    hipEvent_t ev[7] = {};
     wost::DeviceBuffer<float2> d_dverts, d_nverts;
     wost::DeviceBuffer<float> d_seg_phi;
     wost::DeviceBuffer<float> d_table;
@@ -250,6 +251,10 @@ struct wost_handle {
     float2* d_points = nullptr;         // (d_points and d_begin point into d_stage)
     int64_t* d_begin = nullptr;
     wost::DeviceBuffer<double> d_bstats;
+    // weighted channel combinations (wost_solve_range_combined): the weights [L][C] and the
+    // combined block rows [blocks][2L+1] of a solve, and the HIP-event time of its combine kernels
+    wost::DeviceBuffer<double> d_cweights, d_cstats;
+    double combine_ms = 0.0;
     wost::DeviceBuffer<float> d_point_alpha;   // alpha at the query points (delta tracking)
     wost::DeviceBuffer<uint32_t> d_pool;       // walk pools of the tree kernels' workgroups (WalkArgs::pool)
     double tick_khz = 100000.0;       // the device wall clock (hipDeviceAttributeWallClockRate)
@@ -375,6 +380,13 @@ struct SolveOutputs {
     float* walk_values = nullptr;
     uint32_t* walk_steps = nullptr;
     float* records = nullptr;
+    // weighted channel combinations (wost_combine.h; null / 0: none): n_combinations rows of
+    // weights [L][channels], reduced on the device into rows of 2L+1 doubles per block and
+    // per point (the point rows added in block order, like point_stats)
+    const double* weights = nullptr;
+    int32_t n_combinations = 0;
+    double* combined_block_stats = nullptr;
+    double* combined_point_stats = nullptr;
 };
 int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out);
 

@@ -38,6 +38,13 @@ hipError_t launch_block_reduce(const float* val, const uint32_t* steps, const in
                                hipStream_t s, int64_t n_waves = 0, unsigned long long* lstats = nullptr,
                                int first_batch = 1);
 
+// Weighted channel combinations (wost_combine.h): rows of 2L+1 doubles (sum_l, sumsq_l for
+// each of the L = n_combinations rows of weights [L][n_channels], a device array, then the
+// block's steps) of the same blocks, in wost_block_reduce's summation order.
+hipError_t launch_block_combine(const float* val, const uint32_t* steps, const int64_t* begin, int64_t nblocks,
+                                int n_channels, const double* weights, int n_combinations, double* out,
+                                hipStream_t s);
+
 hipError_t launch_geometry_query(int op, const float2* verts, int nv, const float2* pts,
                                  const float2* dirs, const float* radii, int64_t n,
                                  float* out_f, uint8_t* out_mask, hipStream_t s);

@@ -9,6 +9,7 @@
 // independent).
 // the interpreting kernels honour WalkArgs::k2[0] (a single wavenumber; wost_walk.h)
 #define WOST_WAVENUMBERS 1
+#include "wost_combine.h"
 #include "wost_device.h"
 #include "wost_internal.h"
 
@@ -487,6 +488,117 @@ hipError_t launch_eval_field(const char* prog, int which, const float2* pts, int
     if (n <= 0) return hipSuccess;
     const int64_t grid = (n + 255) / 256;
     wost_eval_field_kernel<<<(unsigned)grid, 256, 0, s>>>(prog, which, pts, n, out);
+    return hipGetLastError();
+}
+
+// Weighted channel combinations (wost_combine.h): L combinations
+// v_l = sum_c w[l][c] val[walk][c] of the launch's C channels per walk, and per block their
+// (sum, sum^2) in wost_block_reduce's order -- thread t takes walks lo + t, lo + t + 256,
+// ..., then the same halving tree -- in rows of 2L+1 doubles (the block's step sum last).
+// A thread reads its walk's C contiguous floats once (kWide, C a multiple of 4: 16-byte
+// loads, a walk's values then start on a 16-byte boundary) and keeps the 2L accumulators in
+// registers; the weights are uniform, read through the constant address space (scalar
+// loads), so a zero weight's skip is a scalar branch. The next walk's loads are issued
+// before this walk is combined: every load_walk issues the same loads whatever C and the
+// walk are (an index past C reads channel 0 again, a walk past the block's end the block's
+// last walk, both discarded), so that no branch sits between a load and its use and the
+// loads in flight are counted exactly (with loads under `if (c < C)` the compiler waited
+// for all but one of them before the first product).
+// Runs after wost_block_reduce, which keeps the queue head, the statistics and the longest
+// walk to itself.
+template <bool kWide>
+__global__ void __launch_bounds__(kCombineBlock)
+wost_block_combine(const float* __restrict__ val, const uint32_t* __restrict__ steps,
+                   const int64_t* __restrict__ begin, int64_t nblocks, int C, const double* __restrict__ weights,
+                   int L, double* __restrict__ out) {
+    __shared__ double s_sum[kCombineBlock], s_sq[kCombineBlock], s_st[kCombineBlock];
+    const cptr<double> w = (cptr<double>)weights;
+    const int row = 2 * L + 1;
+    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        const int64_t lo = begin[b], hi = begin[b + 1];
+        double s[kCombineMax], q[kCombineMax];
+#pragma unroll
+        for (int l = 0; l < kCombineMax; ++l) s[l] = q[l] = 0.0;
+        uint64_t st = 0;
+        // the C values and the step count of walk min(i, hi - 1) (hi > lo)
+        auto load_walk = [&](int64_t i, float (&x)[kCombineMax], uint32_t& sx) {
+            const int64_t ic = i < hi ? i : hi - 1;
+            const float* const p = val + ic * C;
+            if (kWide) {
+#pragma unroll
+                for (int c4 = 0; c4 < kCombineMax / 4; ++c4) {
+                    const float4 v = reinterpret_cast<const float4*>(p)[4 * c4 < C ? c4 : 0];
+                    x[4 * c4] = v.x, x[4 * c4 + 1] = v.y, x[4 * c4 + 2] = v.z, x[4 * c4 + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < kCombineMax; ++c) x[c] = p[c < C ? c : 0];
+            }
+            sx = steps[ic];
+        };
+        float x[kCombineMax], xn[kCombineMax];
+        uint32_t sx = 0u, sn;
+        if (hi > lo) load_walk(lo + threadIdx.x, x, sx);   // (wave-uniform: an empty block reads nothing)
+        for (int64_t i = lo + threadIdx.x; i < hi; i += kCombineBlock) {
+            load_walk(i + kCombineBlock, xn, sn);
+            st += sx;
+#pragma unroll
+            for (int l = 0; l < kCombineMax; ++l) {
+                if (l < L) {
+                    double v = 0.0;
+#pragma unroll
+                    for (int c = 0; c < kCombineMax; ++c) {
+                        if (c < C) {
+                            const double wc = w[l * C + c];
+                            if (wc != 0.0) v = combine_term(v, wc, (double)x[c]);
+                        }
+                    }
+                    combine_accumulate(s[l], q[l], v);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < kCombineMax; ++c) x[c] = xn[c];
+            sx = sn;
+        }
+#pragma unroll
+        for (int l = 0; l < kCombineMax; ++l) {
+            if (l < L) {
+                s_sum[threadIdx.x] = s[l];
+                s_sq[threadIdx.x] = q[l];
+                if (l == 0) s_st[threadIdx.x] = (double)st;
+                __syncthreads();
+                for (int h = kCombineBlock / 2; h > 0; h >>= 1) {
+                    if ((int)threadIdx.x < h) {
+                        s_sum[threadIdx.x] += s_sum[threadIdx.x + h];
+                        s_sq[threadIdx.x] += s_sq[threadIdx.x + h];
+                        if (l == 0) s_st[threadIdx.x] += s_st[threadIdx.x + h];
+                    }
+                    __syncthreads();
+                }
+                if (threadIdx.x == 0) {
+                    out[row * b + 2 * l] = s_sum[0];
+                    out[row * b + 2 * l + 1] = s_sq[0];
+                    if (l == 0) out[row * b + row - 1] = s_st[0];
+                }
+                __syncthreads();
+            }
+        }
+    }
+}
+
+hipError_t launch_block_combine(const float* val, const uint32_t* steps, const int64_t* begin, int64_t nblocks,
+                                int n_channels, const double* weights, int n_combinations, double* out,
+                                hipStream_t s) {
+    if (nblocks <= 0) return hipSuccess;
+    if (n_channels < 1 || n_channels > kCombineMax || n_combinations < 1 || n_combinations > kCombineMax)
+        return hipErrorInvalidValue;
+    const int grid = (int)(nblocks < 65536 ? nblocks : 65536);
+    if (n_channels % 4 == 0)
+        wost_block_combine<true><<<grid, kCombineBlock, 0, s>>>(val, steps, begin, nblocks, n_channels, weights,
+                                                                n_combinations, out);
+    else
+        wost_block_combine<false><<<grid, kCombineBlock, 0, s>>>(val, steps, begin, nblocks, n_channels, weights,
+                                                                 n_combinations, out);
     return hipGetLastError();
 }
 

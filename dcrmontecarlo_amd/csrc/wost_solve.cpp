@@ -4,6 +4,7 @@
 // Mirrors WostSolver_2D.solve / _solveUnified (solvers/WoStSolver.py:162-353).
 #include <algorithm>
 
+#include "wost_combine.h"
 #include "wost_handle.h"
 
 using namespace wost;
@@ -116,23 +117,29 @@ int check_request(const wost_handle* h, const SolveRequest& rq, SolveRanges* ran
 // 64-byte aligned; the device holds the first two parts in one buffer of the same layout
 // (h->d_points, h->d_begin), so that one copy brings the points and the first batch's block
 // ranges (C2: a copy and its ~6 us gap less). The point list (wost_solve_range_points; n_sel
-// ids, 0: none) has a device buffer of its own (h->d_point_list).
+// ids, 0: none) has a device buffer of its own (h->d_point_list). A solve with L weighted
+// combinations (crow = 2L+1 doubles per block, 0: none) adds their weights [L][C] and the
+// combined block rows at the end.
 struct Staging {
     float* points = nullptr;
     int64_t* begin = nullptr;
     double* bstats = nullptr;
     int32_t* ids = nullptr;
-    size_t pts_bytes = 0, beg_bytes = 0, bs_bytes = 0, ids_bytes = 0;
+    double* cweights = nullptr;
+    double* cstats = nullptr;
+    size_t pts_bytes = 0, beg_bytes = 0, bs_bytes = 0, ids_bytes = 0, cw_bytes = 0, cs_bytes = 0;
 };
 
-int stage_buffers(wost_handle* h, int64_t n_points, int64_t nblk, int row, int64_t n_sel, Staging* st) {
+int stage_buffers(wost_handle* h, int64_t n_points, int64_t nblk, int row, int64_t n_sel, int crow, Staging* st) {
     auto al64 = [](size_t b) { return (b + 63) / 64 * 64; };
     st->pts_bytes = al64(sizeof(float2) * (size_t)std::max<int64_t>(n_points, 1));
     st->beg_bytes = al64(sizeof(int64_t) * (size_t)(nblk + 1));
     st->bs_bytes = al64(sizeof(double) * (size_t)(kLstatsWords + row * nblk));
     st->ids_bytes = al64(sizeof(int32_t) * (size_t)std::max<int64_t>(n_sel, 0));
+    st->cw_bytes = al64(sizeof(double) * (size_t)(crow > 0 ? kCombineMax * kCombineMax : 0));
+    st->cs_bytes = al64(sizeof(double) * (size_t)(crow * nblk));
     const size_t dev_bytes = st->pts_bytes + st->beg_bytes;
-    if (int rc = ensure_pin(h, dev_bytes + st->bs_bytes + st->ids_bytes)) return rc;
+    if (int rc = ensure_pin(h, dev_bytes + st->bs_bytes + st->ids_bytes + st->cw_bytes + st->cs_bytes)) return rc;
     if (int rc = ensure_cap(h->d_stage, (int64_t)dev_bytes)) return rc;
     char* const dev = h->d_stage;
     char* const pin = h->h_pin;
@@ -142,6 +149,8 @@ int stage_buffers(wost_handle* h, int64_t n_points, int64_t nblk, int row, int64
     st->begin = reinterpret_cast<int64_t*>(pin + st->pts_bytes);
     st->bstats = reinterpret_cast<double*>(pin + dev_bytes);
     st->ids = reinterpret_cast<int32_t*>(pin + dev_bytes + st->bs_bytes);
+    st->cweights = reinterpret_cast<double*>(pin + dev_bytes + st->bs_bytes + st->ids_bytes);
+    st->cstats = reinterpret_cast<double*>(pin + dev_bytes + st->bs_bytes + st->ids_bytes + st->cw_bytes);
     return WOST_OK;
 }
 
@@ -399,6 +408,18 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
                                           "charge in its ball: there is no sample point)");
 
     h->timing = wost_timing{};
+    h->combine_ms = 0.0;
+    // weighted combinations of the channels, reduced on the device after the ordinary rows
+    const int L = out.weights ? out.n_combinations : 0;
+    const int crow = L > 0 ? 2 * L + 1 : 0;   // doubles per combined block / point row
+    if (out.weights || out.n_combinations != 0) {
+        char msg[128];
+        if (combine_check_weights(out.weights, out.n_combinations, ns, msg, sizeof(msg)))
+            return fail(WOST_ERR_INVALID_ARG, "weighted combinations: %s", msg);
+        if (out.records) return fail(WOST_ERR_UNSUPPORTED, "wost_solve_history takes no weighted combinations");
+    }
+    if (out.combined_point_stats)
+        std::fill(out.combined_point_stats, out.combined_point_stats + (size_t)crow * rq.rows(), 0.0);
     if (out.records && listed) return fail(WOST_ERR_UNSUPPORTED, "wost_solve_history takes no point list");
     if (out.point_stats) std::fill(out.point_stats, out.point_stats + row * rq.rows(), 0.0);
     if (R.nblk == 0) return WOST_OK;
@@ -419,12 +440,19 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
                     (long long)R.Wr, (long long)batch_limit);
 
     Staging st;
-    if ((rc = stage_buffers(h, n_points, R.nblk, row, listed ? R.n_sel : 0, &st)) != WOST_OK) return rc;
+    if ((rc = stage_buffers(h, n_points, R.nblk, row, listed ? R.n_sel : 0, crow, &st)) != WOST_OK) return rc;
     std::memcpy(st.points, rq.points, sizeof(float2) * (size_t)n_points);
     if (listed) {   // the point list, through the staging (its copy is done when the solve's last wait is)
         if ((rc = ensure_cap(h->d_point_list, R.n_sel)) != WOST_OK) return rc;
         std::memcpy(st.ids, rq.point_ids, sizeof(int32_t) * (size_t)R.n_sel);
         HIP_TRY(hipMemcpyAsync(h->d_point_list, st.ids, sizeof(int32_t) * (size_t)R.n_sel, hipMemcpyHostToDevice, h->stream));
+    }
+    if (L > 0) {   // the weights, through the staging like the point list; the combined rows' buffer
+        if ((rc = ensure_cap(h->d_cweights, kCombineMax * kCombineMax)) != WOST_OK) return rc;
+        if ((rc = ensure_cap(h->d_cstats, R.nblk * crow)) != WOST_OK) return rc;
+        std::memcpy(st.cweights, out.weights, sizeof(double) * (size_t)(L * ns));
+        HIP_TRY(hipMemcpyAsync(h->d_cweights, st.cweights, sizeof(double) * (size_t)(L * ns), hipMemcpyHostToDevice,
+                               h->stream));
     }
     // the points go with the first batch's block ranges, unless the query points' alpha
     // (delta tracking) needs them first
@@ -468,7 +496,7 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
     HIP_TRY(hipEventRecord(h->ev[4], h->stream));
     int64_t walks_done = 0;
     int launches = 0;
-    double walk_ms = 0.0, red_ms = 0.0;
+    double walk_ms = 0.0, red_ms = 0.0, comb_ms = 0.0;
     for (int64_t j = R.block_begin; j < R.block_end; j = b.j2) {
         // plan the batch: blocks [j, b.j2), b.count walks
         if (!next_batch(R, j, batch_limit, &b)) return fail(WOST_ERR_INVALID_ARG, "internal: block larger than a batch");
@@ -511,6 +539,11 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
                                     launches == 0 ? 1 : 0));   // (the tree kernels keep no wave records)
         h->counter_zero = true;
         HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+        if (L > 0) {   // the combinations of the same per-walk values: one more read of d_val
+            HIP_TRY(launch_block_combine(h->d_val, h->d_steps, h->d_begin, nb, ns, h->d_cweights, L,
+                                         h->d_cstats + (size_t)crow * (j - R.block_begin), h->stream));
+            HIP_TRY(hipEventRecord(h->ev[6], h->stream));
+        }
 
         // copy out the per-walk results, and wait
         if (out.walk_values)
@@ -525,16 +558,24 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
         if (b.j2 >= R.block_end) {   // the last batch: the block sums ride the same wait
             HIP_TRY(hipMemcpyAsync(st.bstats, h->d_bstats, sizeof(double) * (kLstatsWords + row * R.nblk),
                                    hipMemcpyDeviceToHost, h->stream));
+            if (L > 0)
+                HIP_TRY(hipMemcpyAsync(st.cstats, h->d_cstats, sizeof(double) * (size_t)(crow * R.nblk),
+                                       hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipEventRecord(h->ev[5], h->stream));
             HIP_TRY(hipEventSynchronize(h->ev[5]));
         } else {
-            HIP_TRY(hipEventSynchronize(h->ev[2]));
+            HIP_TRY(hipEventSynchronize(h->ev[L > 0 ? 6 : 2]));
         }
         float t0 = 0.f, t1 = 0.f;
         HIP_TRY(hipEventElapsedTime(&t0, h->ev[0], h->ev[1]));
         HIP_TRY(hipEventElapsedTime(&t1, h->ev[1], h->ev[2]));
         walk_ms += t0;
         red_ms += t1;
+        if (L > 0) {
+            float t2 = 0.f;
+            HIP_TRY(hipEventElapsedTime(&t2, h->ev[2], h->ev[6]));
+            comb_ms += t2;
+        }
         ++launches;
         walks_done += count;
     }
@@ -554,6 +595,16 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
         }
     }
     if (out.block_stats) std::memcpy(out.block_stats, bs, sizeof(double) * row * R.nblk);
+    if (L > 0) {   // the combined rows: the same block order
+        if (out.combined_point_stats)
+            for (int64_t k = 0; k < R.nblk; ++k) {
+                const int64_t p = R.point_of(R.block_begin + k);
+                for (int c = 0; c < crow; ++c) out.combined_point_stats[crow * p + c] += st.cstats[crow * k + c];
+            }
+        if (out.combined_block_stats)
+            std::memcpy(out.combined_block_stats, st.cstats, sizeof(double) * (size_t)(crow * R.nblk));
+        h->combine_ms = comb_ms;
+    }
     h->timing.walk_kernel_ms = walk_ms;
     h->timing.reduce_kernel_ms = red_ms;
     h->timing.total_ms = tt;

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <chrono>
 
+#include "wost_combine.h"
 #include "wost_handle.h"
 
 using namespace wost;
@@ -53,6 +54,9 @@ struct Stitch {
     int ns = 1;            // values per walk
     int64_t w_begin = 0, Wr = 0, nbr = 0;
     std::vector<double> all, part;   // block rows of the range / of a piece
+    std::vector<double> call, cpart;   // ... and their weighted combinations' (rows of crow doubles; 0: none)
+    int crow = 0;
+    double combine_ms = 0.0;
     std::vector<float> pv;
     std::vector<uint32_t> ps;
     wost_timing acc{};
@@ -60,7 +64,9 @@ struct Stitch {
 
     Stitch(const SolveRequest& whole, const SolveOutputs& o, int ns_, int64_t w0, int64_t w1)
         : rq(whole), out(o), ns(ns_), w_begin(w0), Wr(w1 - w0), nbr((w1 - w0 + WOST_BLOCK_WALKS - 1) / WOST_BLOCK_WALKS),
-          all((size_t)whole.rows() * nbr * (2 * ns_ + 1)) {}
+          all((size_t)whole.rows() * nbr * (2 * ns_ + 1)), crow(o.weights ? 2 * o.n_combinations + 1 : 0) {
+        if (crow > 0) call.resize((size_t)whole.rows() * nbr * crow);
+    }
 };
 
 // Solves walks [c0, c1) of every point into the stitched solve's outputs and timing.
@@ -79,12 +85,21 @@ int solve_piece(wost_handle* h, Stitch& s, int64_t c0, int64_t c1) {
     piece.block_stats = s.part.data();
     piece.walk_values = s.out.walk_values ? s.pv.data() : nullptr;
     piece.walk_steps = s.out.walk_steps ? s.ps.data() : nullptr;
+    if (s.crow > 0) {
+        s.cpart.resize((size_t)n_points * nbc * s.crow);
+        piece.weights = s.out.weights;
+        piece.n_combinations = s.out.n_combinations;
+        piece.combined_block_stats = s.cpart.data();
+    }
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = solve_impl(h, s.rq, piece);
     s.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (rc != WOST_OK) return rc;
     for (int64_t p = 0; p < n_points; ++p) {
         std::memcpy(&s.all[((size_t)p * s.nbr + boff) * row], &s.part[(size_t)p * nbc * row], sizeof(double) * nbc * row);
+        if (s.crow > 0)
+            std::memcpy(&s.call[((size_t)p * s.nbr + boff) * s.crow], &s.cpart[(size_t)p * nbc * s.crow],
+                        sizeof(double) * nbc * s.crow);
         if (s.out.walk_values)
             std::memcpy(s.out.walk_values + ((size_t)p * s.Wr + woff) * s.ns, &s.pv[(size_t)p * wc * s.ns],
                         sizeof(float) * wc * s.ns);
@@ -92,18 +107,23 @@ int solve_piece(wost_handle* h, Stitch& s, int64_t c0, int64_t c1) {
             std::memcpy(s.out.walk_steps + (size_t)p * s.Wr + woff, &s.ps[(size_t)p * wc], sizeof(uint32_t) * wc);
     }
     add_timing(s.acc, h->timing);
+    s.combine_ms += h->combine_ms;
     return WOST_OK;
 }
 
 // The stitched solve's block rows and point sums (in the range's block order) to the caller.
-void stitched_stats(const Stitch& s) {
-    const int row = 2 * s.ns + 1;
-    if (s.out.block_stats) std::memcpy(s.out.block_stats, s.all.data(), sizeof(double) * s.all.size());
-    if (!s.out.point_stats) return;
-    std::fill(s.out.point_stats, s.out.point_stats + (size_t)row * s.rq.rows(), 0.0);
+void stitched_rows(const Stitch& s, const std::vector<double>& all, int row, double* block_stats, double* point_stats) {
+    if (block_stats) std::memcpy(block_stats, all.data(), sizeof(double) * all.size());
+    if (!point_stats) return;
+    std::fill(point_stats, point_stats + (size_t)row * s.rq.rows(), 0.0);
     for (int64_t p = 0; p < s.rq.rows(); ++p)
         for (int64_t k = 0; k < s.nbr; ++k)
-            for (int c = 0; c < row; ++c) s.out.point_stats[(size_t)row * p + c] += s.all[((size_t)p * s.nbr + k) * row + c];
+            for (int c = 0; c < row; ++c) point_stats[(size_t)row * p + c] += all[((size_t)p * s.nbr + k) * row + c];
+}
+
+void stitched_stats(const Stitch& s) {
+    stitched_rows(s, s.all, 2 * s.ns + 1, s.out.block_stats, s.out.point_stats);
+    if (s.crow > 0) stitched_rows(s, s.call, s.crow, s.out.combined_block_stats, s.out.combined_point_stats);
 }
 
 // A whole single-source solve whose field-specialised kernel is in no cache (option
@@ -188,6 +208,32 @@ SolveOutputs outputs(double* block_stats, double* point_stats, float* walk_value
                         .walk_steps = walk_steps, .records = records};
 }
 
+// wost_solve_range_points' body: one solve, or block-aligned pieces stitched.
+int solve_range(wost_handle* h, SolveRequest rq, const SolveOutputs& out, int64_t walk_begin, int64_t walk_end) {
+    const int64_t W = rq.W, n_points = rq.n_points, n_ids = rq.n_ids;
+    const int32_t* const point_ids = rq.point_ids;
+    // the whole range of every point: an ordinary solve (of a list: a range all the same)
+    if (walk_begin == 0 && walk_end == W && !point_ids) return solve_impl(h, rq, out);
+    const int ns = h->channels();
+    const int64_t chunk = (kMaxBatchWalks / ns) / WOST_BLOCK_WALKS * WOST_BLOCK_WALKS;   // walks of a point per launch
+    if (walk_end - walk_begin <= chunk || walk_begin < 0 || walk_end <= walk_begin || n_points <= 0 ||
+        (point_ids && n_ids < 1)) {
+        rq.block_end = 0;   // (a range names its walks only)
+        rq.walk_begin = walk_begin;
+        rq.walk_end = walk_end;
+        return solve_impl(h, rq, out);
+    }
+    // a range longer than one launch holds per point: block-aligned sub-ranges, one solve
+    // each, scattered into the range's layout; point sums in the range's block order
+    Stitch st(rq, out, ns, walk_begin, walk_end);
+    for (int64_t c0 = walk_begin; c0 < walk_end; c0 += chunk)
+        if (int rc = solve_piece(h, st, c0, std::min(walk_end, c0 + chunk))) return rc;
+    stitched_stats(st);
+    h->timing = st.acc;
+    h->combine_ms = st.combine_ms;
+    return WOST_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -224,25 +270,46 @@ int wost_solve_range_points(wost_handle* h, const float* points, int64_t n_point
     rq.multi = true;
     rq.point_ids = point_ids;   // (null: every point, wost_solve_range)
     rq.n_ids = point_ids ? n_ids : 0;
-    const SolveOutputs out = outputs(block_stats, point_stats, walk_values, walk_steps);
-    // the whole range of every point: an ordinary solve (of a list: a range all the same)
-    if (walk_begin == 0 && walk_end == W && !point_ids) return solve_impl(h, rq, out);
-    const int ns = h->channels();
-    const int64_t chunk = (kMaxBatchWalks / ns) / WOST_BLOCK_WALKS * WOST_BLOCK_WALKS;   // walks of a point per launch
-    if (walk_end - walk_begin <= chunk || walk_begin < 0 || walk_end <= walk_begin || n_points <= 0 ||
-        (point_ids && n_ids < 1)) {
-        rq.block_end = 0;   // (a range names its walks only)
-        rq.walk_begin = walk_begin;
-        rq.walk_end = walk_end;
-        return solve_impl(h, rq, out);
-    }
-    // a range longer than one launch holds per point: block-aligned sub-ranges, one solve
-    // each, scattered into the range's layout; point sums in the range's block order
-    Stitch st(rq, out, ns, walk_begin, walk_end);
-    for (int64_t c0 = walk_begin; c0 < walk_end; c0 += chunk)
-        if (int rc = solve_piece(h, st, c0, std::min(walk_end, c0 + chunk))) return rc;
-    stitched_stats(st);
-    h->timing = st.acc;
+    return solve_range(h, rq, outputs(block_stats, point_stats, walk_values, walk_steps), walk_begin, walk_end);
+}
+
+int wost_solve_range_combined(wost_handle* h, const float* points, int64_t n_points, const int32_t* point_ids,
+                              int64_t n_ids, int64_t W, int64_t walk_begin, int64_t walk_end, int32_t max_steps,
+                              float eps, uint64_t seed, const double* weights, int32_t n_combinations,
+                              double* block_stats, double* point_stats, double* channel_point_stats) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    char msg[128];
+    if (combine_check_weights(weights, n_combinations, h->channels(), msg, sizeof(msg)))
+        return fail(WOST_ERR_INVALID_ARG, "wost_solve_range_combined: %s", msg);
+    SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
+    rq.multi = true;
+    rq.point_ids = point_ids;
+    rq.n_ids = point_ids ? n_ids : 0;
+    SolveOutputs out = outputs(nullptr, channel_point_stats, nullptr, nullptr);
+    out.weights = weights;
+    out.n_combinations = n_combinations;
+    out.combined_block_stats = block_stats;
+    out.combined_point_stats = point_stats;
+    return solve_range(h, rq, out, walk_begin, walk_end);
+}
+
+int wost_combine_blocks_host(const float* values, const int64_t* begin, int64_t n_blocks, int32_t n_channels,
+                             const double* weights, int32_t n_combinations, double* out) {
+    char msg[128];
+    if (combine_check_weights(weights, n_combinations, n_channels, msg, sizeof(msg)))
+        return fail(WOST_ERR_INVALID_ARG, "wost_combine_blocks_host: %s", msg);
+    if (n_blocks < 0 || !begin || !out || (n_blocks > 0 && begin[n_blocks] > begin[0] && !values))
+        return fail(WOST_ERR_INVALID_ARG, "wost_combine_blocks_host: bad arguments");
+    for (int64_t b = 0; b < n_blocks; ++b)
+        if (begin[b] < 0 || begin[b + 1] < begin[b])
+            return fail(WOST_ERR_INVALID_ARG, "wost_combine_blocks_host: block %lld's range is not ascending", (long long)b);
+    combine_blocks_host(values, begin, n_blocks, n_channels, weights, n_combinations, out);
+    return WOST_OK;
+}
+
+int wost_last_combine_ms(const wost_handle* h, double* ms) {
+    if (!h || !ms) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
+    *ms = h->combine_ms;
     return WOST_OK;
 }
 

@@ -182,6 +182,23 @@ def run_to_tolerance(run_round, n_points: int, n_channels: int, *, rel_tol: floa
     return sums, walks, converged, rounds
 
 
+def _range_layout(n_points: int, point_ids, walk_begin, walk_end):
+    """The output layout of a walk-range solve (solve_range, solve_range_combinations):
+    (point_ids as int32 or None, point rows, blocks per point). ValueError on an empty list
+    or ids that are not 32-bit integers; the library checks their order and range."""
+    ids = None
+    if point_ids is not None:
+        ids = np.ascontiguousarray(np.asarray(_np(point_ids)).ravel())
+        if ids.size == 0:
+            raise ValueError("point_ids must hold at least one point")
+        if (not np.issubdtype(ids.dtype, np.integer) or ids.min() < -2**31 or ids.max() >= 2**31):
+            raise ValueError("point_ids must be integers that fit 32 bits")
+        ids = ids.astype(np.int32)
+    rows = n_points if ids is None else ids.shape[0]
+    nbr = -(-(int(walk_end) - int(walk_begin)) // _lib.WOST_BLOCK_WALKS)
+    return ids, rows, nbr
+
+
 def _problem(dxy, nxy, g, f, sigma, alpha, compat, device, sigma_bar):
     """wost_problem for the given geometry and fields (None = absent; the library
     applies the sigma = 0 / alpha = 1 defaults itself) and the objects to keep alive."""
@@ -489,16 +506,7 @@ class WostSolver_2D:
         / uint32 [rows, walk_end - walk_begin] arrays that receive the per-walk results."""
         p = _points_np(solvePoints)
         n = p.shape[0]
-        ids = None
-        if point_ids is not None:
-            ids = np.ascontiguousarray(np.asarray(_np(point_ids)).ravel())
-            if ids.size == 0:
-                raise ValueError("point_ids must hold at least one point")
-            if (not np.issubdtype(ids.dtype, np.integer) or ids.min() < -2**31 or ids.max() >= 2**31):
-                raise ValueError("point_ids must be integers that fit 32 bits")
-            ids = ids.astype(np.int32)
-        rows = n if ids is None else ids.shape[0]
-        nbr = -(-(int(walk_end) - int(walk_begin)) // _lib.WOST_BLOCK_WALKS)
+        ids, rows, nbr = _range_layout(n, point_ids, walk_begin, walk_end)
         ns = ctypes.c_int32(1)   # values per walk: sources x wavenumbers
         _lib.check(_lib.lib.wost_num_channels(self._h, ctypes.byref(ns)), "wost_num_channels")
         for a, dt, size in ((walk_values, np.float32, ns.value), (walk_steps, np.uint32, 1)):
@@ -519,8 +527,132 @@ class WostSolver_2D:
         self.last_timing = self.timing()
         return bs
 
+    def _combination_weights(self, weights) -> np.ndarray:
+        """``weights`` as contiguous float64 [L, C] for the C installed channels (ValueError
+        on another width; the library checks L and the values)."""
+        w = np.ascontiguousarray(np.atleast_2d(np.asarray(_np(weights), np.float64)))
+        C = self.num_channels()
+        if w.ndim != 2 or w.shape[1] != C:
+            raise ValueError(f"weights must have shape [L, {C}] for the {C} installed channels, got {w.shape}")
+        return w
+
+    def solve_range_combinations(self, solvePoints, weights, nWalks: int, walk_begin: int, walk_end: int,
+                                 maxSteps: int = 1000, eps: float = 1e-4, seed: int = 0, point_ids=None,
+                                 point_sums: np.ndarray | None = None,
+                                 channel_point_sums: np.ndarray | None = None):
+        """``solve_range`` with L weighted combinations of the C installed channels reduced on
+        the device (wost_solve_range_combined): ``weights`` [L, C]; walk i's
+        combination l is sum_c weights[l, c] * value[i, c] in float64, product and sum rounded
+        separately, zero weights skipped. Returns the block rows [rows, blocks, 2L+1] of
+        (sum_l, sum^2_l, ..., steps); a unit row's entries are bit for bit that channel's of
+        ``solve_range``. No per-walk value leaves the device. ``point_ids`` as in
+        ``solve_range``. point_sums: an optional float64 [rows, 2L+1] array that receives the
+        point rows (the block rows added in block order); channel_point_sums: an optional
+        float64 [rows, 2C+1] array that receives the channels' own point rows (``solve_range``'s).
+        ``last_combine_ms`` is the HIP-event time of the combine kernels."""
+        p = _points_np(solvePoints)
+        n = p.shape[0]
+        w = self._combination_weights(weights)
+        L, C = w.shape
+        ids, rows, nbr = _range_layout(n, point_ids, walk_begin, walk_end)
+        cps = channel_point_sums
+        for a, width in ((point_sums, 2 * L + 1), (cps, 2 * C + 1)):
+            if a is not None and (a.dtype != np.float64 or not a.flags.c_contiguous or a.size != rows * width):
+                raise ValueError("point_sums / channel_point_sums: contiguous float64 [rows, 2L+1] / [rows, 2C+1]")
+        bs = np.zeros((rows, max(nbr, 0), 2 * L + 1), np.float64)
+        rc = _lib.lib.wost_solve_range_combined(
+            self._h, _lib.fptr(p), n, None if ids is None else ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            rows if ids is not None else 0, int(nWalks), int(walk_begin), int(walk_end), int(maxSteps), float(eps),
+            int(seed) & (2**64 - 1), _lib.dptr(w), L, _lib.dptr(bs), _lib.dptr(point_sums), _lib.dptr(cps))
+        _lib.check(rc, "WostSolver_2D.solve_range_combinations")
+        self.last_timing = self.timing()
+        return bs
+
+    @property
+    def last_combine_ms(self) -> float:
+        """HIP-event time of the combine kernels of the solver's last solve (wost_last_combine_ms):
+        0.0 when that solve reduced no combinations, or before any solve."""
+        ms = ctypes.c_double(0.0)
+        _lib.check(_lib.lib.wost_last_combine_ms(self._h, ctypes.byref(ms)), "wost_last_combine_ms")
+        return float(ms.value)
+
+    def solve_combinations(self, solvePoints, weights, nWalks=1000, maxSteps=1000, eps=1e-4, *, seed: int = 0,
+                           return_stats: bool = False):
+        """Mean (float32 [L, N]) of L weighted combinations ``weights`` [L, C] of the C
+        installed channels (sources, wavenumbers, models, point sources), and with
+        ``return_stats`` a SolveStats whose mean and stderr are [L, N]. The channels share
+        their walks, so the standard error comes from the per-walk combined values, formed and
+        reduced on the device (``solve_range_combinations``); the point rows are the block
+        rows added in block order and are kept in ``last_point_sums`` [N, 2L+1]."""
+        p = _points_np(solvePoints)
+        nWalks = int(nWalks)
+        if nWalks < 1:
+            raise ValueError("nWalks must be >= 1")
+        bs = self.solve_range_combinations(p, weights, nWalks, 0, nWalks, maxSteps, eps, seed)
+        n, nbr, row = bs.shape
+        sums = np.zeros((n, row), np.float64)
+        for k in range(nbr):
+            sums = sums + bs[:, k, :]
+        self.last_point_sums = sums
+        mean, se, _ = tolerance_rule(sums, nWalks, 0.0, 0.0)
+        u = mean.astype(np.float32)
+        if not return_stats:
+            return u
+        t = self.last_timing
+        return u, SolveStats(mean=mean, stderr=se, mean_steps=sums[:, -1] / nWalks, walks=nWalks,
+                             total_steps=int(t["total_steps"]), kernel_ms=t["walk_kernel_ms"], total_ms=t["total_ms"])
+
+    def solve_models_differences(self, solvePoints, models, nWalks=1000, maxSteps=1000, eps=1e-4, *, sources=None,
+                                 k=None, seed: int = 0):
+        """Paired differences v_m - v_0 of models solved on shared paths, reduced on the
+        device: (mean, stderr) of float64 [M-1, N] ([M-1, S, N], [M-1, K, N] or [M-1, K, S, N]
+        with ``sources`` / ``k``), ``solve_models``' output shape without model 0, the
+        standard error from the per-walk differences (``survey.paired_difference`` without the
+        per-walk values on the host). All M*K*S channels must fit one launch
+        (WOST_MAX_SOURCES; the (M-1)*K*S rows then fit too): ValueError otherwise -- use
+        ``solve_models_walks`` with ``survey.paired_difference`` then. The solver's models,
+        wavenumbers and source are restored afterwards."""
+        from ..survey import difference_weights
+
+        mods = self.model_fields(models)
+        if len(mods) < 2:
+            raise ValueError("solve_models_differences needs at least two models")
+        if sources is not None and any(is_point_source(s) for s in sources):
+            raise NotImplementedError("solve_models scores source fields: point sources under several models are "
+                                      "not supported")
+        fields = None if sources is None else self.source_fields(sources)
+        kk = None if k is None else np.atleast_1d(np.asarray(k, np.float64)).ravel()
+        if kk is not None and kk.size < 1:
+            raise ValueError("k must hold at least one wavenumber")
+        M, S, K = len(mods), 1 if fields is None else len(fields), 1 if kk is None else kk.size
+        cap = _lib.WOST_MAX_SOURCES
+        if M * K * S > cap:   # (the (M - 1) K S rows then fit too)
+            raise ValueError(f"{M} models x {K} wavenumbers x {S} sources are {M * K * S} channels, more than one "
+                             f"launch's {cap}: use solve_models_walks with survey.paired_difference")
+        w = difference_weights(M, K, S)
+        saved_k, saved_m = self.wavenumbers, getattr(self, "models", None)
+        self.set_wavenumbers(None)   # (the setters check models x wavenumbers x sources)
+        self.set_models(None)
+        try:
+            with (contextlib.nullcontext() if fields is None else self.sources_installed(fields)):
+                try:
+                    self.set_models(mods)
+                    if kk is not None:
+                        self.set_wavenumbers(kk)
+                    _, st = self.solve_combinations(solvePoints, w, nWalks, maxSteps, eps, seed=seed, return_stats=True)
+                finally:
+                    self.set_wavenumbers(None)
+                    self.set_models(None)
+        finally:
+            self.set_models(saved_m)
+            self.set_wavenumbers(saved_k)
+        n = st.mean.shape[1]
+        shape = (M - 1,) + ((K,) if k is not None else ()) + ((S,) if sources is not None else ()) + (n,)
+        return st.mean.reshape(shape), st.stderr.reshape(shape)
+
     def solve_to_tolerance(self, solvePoints, *, rel_tol: float = 0.0, abs_tol: float = 0.0, min_walks: int = 16384,
-                           max_walks: int, maxSteps: int = 1000, eps: float = 1e-4, seed: int = 0):
+                           max_walks: int, maxSteps: int = 1000, eps: float = 1e-4, seed: int = 0,
+                           combinations=None):
         """Solve each point to a target standard error instead of a fixed walk count: a point
         stops once stderr <= max(abs_tol, rel_tol * |mean|) in every channel, or at
         ``max_walks``. Walks run in rounds over the points still unconverged only (DESIGN.md
@@ -540,15 +672,29 @@ class WostSolver_2D:
         no point is judged on fewer walks. A channel whose walks all scored an exact 0 is not
         taken as converged to a relative tolerance (only with abs_tol > 0); NaN never converges.
 
+        combinations: weights [L, C] (``solve_range_combinations``): the rule then acts on the L
+        weighted combinations of the channels instead of the channels themselves -- in a 2.5-D
+        solve the transformed potential (``wavenumber.transform_weights``), whose high
+        wavenumbers are tiny and noisy and never meet a relative tolerance of their own. The
+        rounds then reduce the combinations on the device, ``u`` is float32 [L, N] and the
+        stats' ``sums`` are [N, 2L+1], bit for bit ``solve_range_combinations(0, n_p)``'s point
+        rows. ``None`` (default): the channels, as above.
+
         Returns ``(u, stats)``: u float32 [N, 1] ([C, N] with C > 1 channels; a torch tensor if
         the points were one) and a :class:`ToleranceStats`. Needs the field-specialised kernel."""
         p = _points_np(solvePoints)
         n = p.shape[0]
         C = self.num_channels()
+        cw = None if combinations is None else self._combination_weights(combinations)
+        if cw is not None:
+            C = cw.shape[0]   # (the rule's channels: the combinations)
         acc = {"steps": 0, "kernel_ms": 0.0, "total_ms": 0.0}
 
         def run_round(ids, w0, w1):
-            bs = self.solve_range(p, int(max_walks), w0, w1, maxSteps, eps, seed, point_ids=ids)
+            if cw is None:
+                bs = self.solve_range(p, int(max_walks), w0, w1, maxSteps, eps, seed, point_ids=ids)
+            else:
+                bs = self.solve_range_combinations(p, cw, int(max_walks), w0, w1, maxSteps, eps, seed, point_ids=ids)
             t = self.last_timing
             acc["steps"] += int(t["total_steps"])
             acc["kernel_ms"] += float(t["walk_kernel_ms"])
@@ -559,7 +705,7 @@ class WostSolver_2D:
                                                           min_walks=min_walks, max_walks=max_walks)
         mean, se, _ = tolerance_rule(sums, np.maximum(walks, 1), rel_tol, abs_tol)
         self.last_point_sums = sums
-        if C == 1:
+        if C == 1 and cw is None:
             mean, se = mean[0], se[0]
             u = _like(mean.astype(np.float32).reshape(n, 1), solvePoints)
         else:

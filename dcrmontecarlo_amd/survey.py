@@ -186,6 +186,20 @@ def paired_difference(walks: np.ndarray):
     return mean, np.sqrt(var / w)
 
 
+def difference_weights(M: int, K: int = 1, S: int = 1) -> np.ndarray:
+    """Weight rows of the paired differences v_m - v_0 for ``WostSolver_2D.solve_combinations``
+    (DESIGN.md 7e): float64 [(M - 1) K S, M K S], row ((m - 1) K + j) S + s holding +1 at channel
+    (m K + j) S + s and -1 at channel j S + s, for m >= 1 (the channel order of set_models)."""
+    M, K, S = int(M), int(K), int(S)
+    if M < 2 or K < 1 or S < 1:
+        raise ValueError("difference_weights needs M >= 2 models and K, S >= 1")
+    w = np.zeros(((M - 1) * K * S, M * K * S), np.float64)
+    r = np.arange((M - 1) * K * S)
+    w[r, r + K * S] = 1.0
+    w[r, r % (K * S)] = -1.0
+    return w
+
+
 def paired_apparent_resistivity(model_walks: np.ndarray, bg_walks: np.ndarray, pairs: np.ndarray,
                                 rho_bg: float) -> ApparentResistivity:
     """rho_a from per-walk values [E, W] of the model and the background solved on

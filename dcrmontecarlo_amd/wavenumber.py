@@ -134,15 +134,77 @@ def wavenumber_groups(k, groups: int = 1):
     return [g for g in np.array_split(order, max(1, min(int(groups), len(order)))) if len(g)]
 
 
+def transform_weights(w, n_sources: int = 1) -> np.ndarray:
+    """Weight rows of the inverse transform for ``WostSolver_2D.solve_combinations``: float64
+    [S, K*S], row s holding the quadrature weight w[j] at channel j*S + s (wavenumber j major,
+    source s minor: set_wavenumbers' channel order) and 0 elsewhere."""
+    w = np.asarray(w, np.float64).ravel()
+    S, K = int(n_sources), w.size
+    if S < 1 or K < 1:
+        raise ValueError("transform_weights needs at least one weight and one source")
+    out = np.zeros((S, K * S), np.float64)
+    for s in range(S):
+        out[s, s::S] = w
+    return out
+
+
+def _are_point_sources(sources) -> bool:
+    from .solvers.WoStSolver import is_point_source
+
+    return all(is_point_source(s) or isinstance(s, (list, tuple)) for s in sources)
+
+
+def _one_launch(solver, sources, n_k: int) -> bool:
+    """Whether ``sources`` x n_k wavenumbers fit one launch of ``solver`` (point sources: also
+    the charges, WOST_MAX_POINT_CHARGES)."""
+    from . import _lib
+
+    if len(sources) * n_k > _lib.WOST_MAX_SOURCES:
+        return False
+    return not _are_point_sources(sources) or len(solver._point_source_chunks(sources, n_k)) == 1
+
+
+def _transformed_group_device(solver, pts, sources, kk, ww, n_walks, max_steps, eps, seed):
+    """One launch's sum_j w_j u_{k_j} of its sources, reduced on the device: a SolveStats with
+    [S, N] mean and stderr. The solver's wavenumbers and source are restored."""
+    points = _are_point_sources(sources)
+    saved = solver.wavenumbers
+    solver.set_wavenumbers(None)   # (the setters check sources x wavenumbers)
+    try:
+        ctx = (solver.point_sources_installed(sources) if points
+               else solver.sources_installed(solver.source_fields(sources)))
+        with ctx:
+            try:
+                solver.set_wavenumbers(kk)
+                _, st = solver.solve_combinations(pts, transform_weights(ww, len(sources)), n_walks, max_steps, eps,
+                                                  seed=seed, return_stats=True)
+            finally:
+                solver.set_wavenumbers(None)
+    finally:
+        solver.set_wavenumbers(saved)
+    return st
+
+
 def transformed_potentials(solvers, groups, points, sources, k, w, n_walks: int, max_steps: int, eps: float,
-                           seed: int = 0) -> Transformed:
+                           seed: int = 0, device_reduce: bool = False) -> Transformed:
     """sum_j w_j u_{k_j} of every source (fields, or point sources: survey.point_electrode /
     point_dipole, one kind per call) at every point. ``groups``: index arrays into k,
     group g solved by ``solvers[g]`` (wavenumber_groups). Within a group all channels share
     their walks, so the standard error comes from the per-walk weighted sums
     v = sum_j w_j v_j, never from the channels' own errors (they are correlated); groups
     use different seeds and handles, so their errors add in quadrature. Holds one launch's
-    per-walk values at a time ([16, N, n_walks] floats) and one chunk's weighted sums."""
+    per-walk values at a time ([16, N, n_walks] floats) and one chunk's weighted sums.
+
+    device_reduce: form and reduce the per-walk weighted sums on the device
+    (WostSolver_2D.solve_combinations) wherever a group's wavenumbers and a
+    source chunk fit one launch (WOST_MAX_SOURCES channels): no per-walk value crosses the bus.
+    A group of more wavenumbers than that keeps the host path (a combination across launches
+    needs per-walk state). Mean and standard error then agree with the host path to float64
+    rounding (another summation order), not bit for bit; the default False is the host path.
+    The device's variance is the one-pass (sum v^2 - (sum v)^2 / n) / (n - 1) of its block
+    sums, where numpy's is two-pass: its cancellation error grows like (Q + S^2/n) / (Q - S^2/n)
+    times n 2^-53, so with |mean| >> the per-walk standard deviation the reported error loses
+    digits the host path keeps (a single walk gives 0 on both paths)."""
     k = np.asarray(k, np.float64)
     w = np.asarray(w, np.float64)
     pts = np.asarray(points, np.float32).reshape(-1, 2)
@@ -160,6 +222,15 @@ def transformed_potentials(solvers, groups, points, sources, k, w, n_walks: int,
         for s0 in range(0, S, s_chunk):
             s1 = min(S, s0 + s_chunk)
             k_chunk = max(1, _lib.WOST_MAX_SOURCES // (s1 - s0))
+            if device_reduce and _one_launch(solver, sources[s0:s1], len(idx)):
+                st = _transformed_group_device(solver, pts, sources[s0:s1], k[idx], w[idx], n_walks, max_steps, eps,
+                                               group_seed(seed, g))
+                mean[s0:s1] += st.mean
+                var[s0:s1] += st.stderr ** 2
+                launches += 1
+                ms += solver.last_timing["walk_kernel_ms"]
+                steps += int(solver.last_point_sums[:, -1].sum())
+                continue
             acc = np.zeros((s1 - s0, N, int(n_walks)))
             for j0 in range(0, len(idx), k_chunk):
                 jj = idx[j0:j0 + k_chunk]
@@ -208,7 +279,7 @@ def _solvers_25d(sc: Scenario, k, groups, compat, device, solvers, electrodes="g
 
 
 def _run_25d(sc, quad, tx_cols, dv_of, factor, n_walks, width, n_k, groups, seed, device, compat, solvers,
-             r_min, r_max, electrodes="gaussian"):
+             r_min, r_max, electrodes="gaussian", device_reduce=False):
     if electrodes not in ("gaussian", "point"):
         raise ValueError(f'electrodes must be "gaussian" or "point", got {electrodes!r}')
     E = len(sc.points)
@@ -224,7 +295,8 @@ def _run_25d(sc, quad, tx_cols, dv_of, factor, n_walks, width, n_k, groups, seed
         srcs = [point_dipole(x[a], x[b]) for a, b in tx]
     else:
         srcs = [dipole_source(x[a], x[b], width) for a, b in tx]
-    tr = transformed_potentials(solvers, idx, sc.points, srcs, k, w, n_walks, sc.max_steps, sc.eps, seed)
+    tr = transformed_potentials(solvers, idx, sc.points, srcs, k, w, n_walks, sc.max_steps, sc.eps, seed,
+                                device_reduce=device_reduce)
     row = {(int(a), int(b)): i for i, (a, b) in enumerate(tx)}
     t = np.array([row[(int(q[tx_cols[0]]), int(q[tx_cols[1]]))] for q in quad], np.int64)
     hi, lo = dv_of(quad)
@@ -238,7 +310,7 @@ def _run_25d(sc, quad, tx_cols, dv_of, factor, n_walks, width, n_k, groups, seed
 
 def run_wenner_survey_25d(sc: Scenario, n_walks: int, a: int = 1, width: float = 0.5, n_k: int | None = None,
                           groups=1, seed: int = 0, device: int | None = None, compat: str = "fixed",
-                          solvers=None, electrodes: str = "gaussian") -> Survey25DResult:
+                          solvers=None, electrodes: str = "gaussian", device_reduce: bool = False) -> Survey25DResult:
     """2.5-D Wenner-alpha survey of ``sc`` (its points are the surface electrodes, equally
     spaced; its alpha the conductivity): apparent resistivity of point electrodes,
     rho_a = 2 pi a dV / I with dV = V_M - V_N for the transmitter A+ / B-. Sources x
@@ -252,22 +324,25 @@ def run_wenner_survey_25d(sc: Scenario, n_walks: int, a: int = 1, width: float =
     walks need ~d^2 sigma_bar / 4 steps from Dirichlet distance d (set sc.max_steps).
     electrodes: "gaussian" (default) injects through Gaussians of standard deviation ``width``;
     "point" through point electrodes scored exactly (compat="fixed" only; ``width`` is
-    ignored, and ``sc`` must have no source field: its solvers are built without one)."""
+    ignored, and ``sc`` must have no source field: its solvers are built without one).
+    device_reduce: transformed_potentials' -- the weighted sums formed and reduced on the device
+    (results equal to float64 rounding, not bit for bit; default False)."""
     quad = wenner_quadripoles(len(sc.points), a)
     x = np.asarray(sc.points, np.float64)
     dx = float(np.linalg.norm(x[1] - x[0])) if len(x) > 1 else 1.0
     return _run_25d(sc, quad, [0, 3], lambda q: (q[:, 1], q[:, 2]),
                     lambda q, xy: np.full(len(q), wenner_geometric_factor(a * dx)), n_walks, width, n_k, groups, seed,
-                    device, compat, solvers, a * dx, 2 * a * dx, electrodes)
+                    device, compat, solvers, a * dx, 2 * a * dx, electrodes, device_reduce)
 
 
 def run_dipole_dipole_survey_25d(sc: Scenario, n_walks: int, n_max: int = 4, width: float = 0.5,
                                  n_k: int | None = None, groups=1, seed: int = 0, device: int | None = None,
-                                 compat: str = "fixed", solvers=None, electrodes: str = "gaussian") -> Survey25DResult:
+                                 compat: str = "fixed", solvers=None, electrodes: str = "gaussian",
+                                 device_reduce: bool = False) -> Survey25DResult:
     """2.5-D dipole-dipole pseudosection: quadripoles (A, B, M, N) = (c, c+1, c+1+n, c+2+n),
     n = 1..n_max, rho_a = pi n (n+1) (n+2) a dV / I with dV = V_N - V_M (positive over a
     half-space). The quadrature covers the electrode distances a .. (n_max + 2) a.
-    electrodes: as in run_wenner_survey_25d."""
+    electrodes, device_reduce: as in run_wenner_survey_25d."""
     quad = dipole_dipole_quadripoles(len(sc.points), n_max)
     x = np.asarray(sc.points, np.float64)
     dx = float(np.linalg.norm(x[1] - x[0])) if len(x) > 1 else 1.0
@@ -277,4 +352,4 @@ def run_dipole_dipole_survey_25d(sc: Scenario, n_walks: int, n_max: int = 4, wid
         return np.array([dipole_dipole_geometric_factor(dx, int(v)) for v in n])
 
     return _run_25d(sc, quad, [0, 1], lambda q: (q[:, 3], q[:, 2]), factor, n_walks, width, n_k, groups, seed,
-                    device, compat, solvers, dx, (n_max + 2) * dx, electrodes)
+                    device, compat, solvers, dx, (n_max + 2) * dx, electrodes, device_reduce)

@@ -450,6 +450,43 @@ int wost_solve_range_points(wost_handle* h, const float* points, int64_t n_point
                             double* block_stats, double* point_stats,
                             float* walk_values, uint32_t* walk_steps);
 
+/* Weighted channel combinations, reduced on the device (no reference counterpart; DESIGN.md
+ * 7e). The C = wost_num_channels(h) channels of a launch share their walks and are
+ * correlated, so the standard error of a linear combination sum_c w_c u_c (a 2.5-D
+ * potential sum_j w_j u_{k_j}, a paired difference v_m - v_0) has to come from the
+ * per-walk combined values. With weights [L][C] (row-major, L <= WOST_MAX_SOURCES) walk i
+ * scores, for each row l,
+ *      v_l = 0.0;  for c ascending: v_l = v_l + w[l][c] * (double)value[i][c],
+ * product and sum rounded separately (never fused), a term whose weight is exactly 0.0
+ * skipped -- so a unit row is that channel's value itself, whatever the other channels hold.
+ * sum_l and sum^2_l then accumulate per block in the order of the channels' own sums: a unit
+ * row's (sum, sum^2) are bit for bit that channel's entries of wost_solve_range's rows.
+ *
+ * wost_solve_range_points with L weighted combinations of the C installed channels reduced
+ * on the device. weights [n_combinations][C] row-major, C = wost_num_channels(h).
+ * block_stats [rows][n_range_blocks][2L+1], point_stats [rows][2L+1] (block order), and
+ * optionally channel_point_stats [rows][2C+1], bit for bit wost_solve_range_points' point_stats.
+ * point_ids NULL: every point. The last entry of a row is its step sum, as in the channels'
+ * rows. Nothing per-walk crosses the bus; the combinations cost one more read of the
+ * launch's per-walk values on the device. A range longer than one launch is solved in
+ * block-aligned sub-ranges with the same rows.
+ *   WOST_ERR_INVALID_ARG  n_combinations < 1 or > WOST_MAX_SOURCES, NULL weights, a weight
+ *                         that is not finite; and wost_solve_range_points' refusals. */
+int wost_solve_range_combined(wost_handle* h, const float* points, int64_t n_points,
+                              const int32_t* point_ids, int64_t n_ids, int64_t walks_per_point,
+                              int64_t walk_begin, int64_t walk_end, int32_t max_steps, float eps, uint64_t seed,
+                              const double* weights, int32_t n_combinations,
+                              double* block_stats, double* point_stats, double* channel_point_stats);
+
+/* Host only, no device: the same rows [n_blocks][2L] from per-walk values, op for op.
+ * values [walks][n_channels]; block b covers walks [begin[b], begin[b+1]). The weights'
+ * refusals are wost_solve_range_combined's (n_channels in 1..WOST_MAX_SOURCES). */
+int wost_combine_blocks_host(const float* values, const int64_t* begin, int64_t n_blocks,
+                             int32_t n_channels, const double* weights, int32_t n_combinations, double* out);
+
+/* HIP-event time of the combine kernels of the handle's last solve (0 when it ran none). */
+int wost_last_combine_ms(const wost_handle* h, double* ms);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, RCCL over xGMI. The reference
  * has no parallel code; walks shard trivially, and the only exchange is one
