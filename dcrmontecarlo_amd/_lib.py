@@ -304,6 +304,33 @@ def make_field(field):
     return wf, (T, F, G, wf)
 
 
+def _field_ptr(field, keep: list):
+    wf, k = make_field(field)
+    keep.append(k)
+    return ctypes.pointer(wf) if wf is not None else None
+
+
+def pack_fields(fields):
+    """Fields -> (array of wost_field pointers, keepalive); an empty list gives one NULL entry."""
+    keep = []
+    arr = (POINTER(WostField) * max(1, len(fields)))(*[_field_ptr(f, keep) for f in fields])
+    return arr, keep
+
+
+def pack_models(pairs):
+    """(sigma, alpha) field pairs (None: absent) -> (array of wost_model, keepalive)."""
+    keep = []
+    arr = (WostModel * max(1, len(pairs)))()
+    for m, (sigma, alpha) in enumerate(pairs):
+        arr[m].sigma, arr[m].alpha = _field_ptr(sigma, keep), _field_ptr(alpha, keep)
+    return arr, keep
+
+
+def seed64(seed) -> int:
+    """A seed as the uint64 the library takes (negative seeds wrap)."""
+    return int(seed) & (2**64 - 1)
+
+
 def declared_symbols() -> list[str]:
     """Entry points declared in include/wost.h (for the export check)."""
     import re

@@ -408,12 +408,10 @@ class Communicator:
 def _distributed_sums(solver, comm: Communicator, p: np.ndarray, nWalks: int, maxSteps: int, eps: float,
                       seed: int):
     n = p.shape[0]
-    ns = ctypes.c_int32(1)   # values per walk: models x wavenumbers x sources (rows of 2C+1)
-    _lib.check(_lib.lib.wost_num_channels(solver._h, ctypes.byref(ns)), "wost_num_channels")
-    sums = np.zeros((n, 2 * ns.value + 1), np.float64)
+    sums = np.zeros((n, 2 * solver.num_channels() + 1), np.float64)   # (models x wavenumbers x sources: rows of 2C+1)
     t = _lib.WostDistTiming()
     _lib.check(_lib.lib.wost_solve_distributed(solver._h, comm._c, _lib.fptr(p), n, int(nWalks), int(maxSteps),
-                                               float(eps), int(seed) & (2**64 - 1), _lib.dptr(sums), ctypes.byref(t)),
+                                               float(eps), _lib.seed64(seed), _lib.dptr(sums), ctypes.byref(t)),
                "wost_solve_distributed", comm=True)
     timing = {k: getattr(t.local, k) for k, _ in _lib.WostTiming._fields_}
     timing.update({"walk_begin": int(t.walk_begin), "walk_end": int(t.walk_end), "all_steps": int(t.total_steps),
@@ -446,7 +444,7 @@ def solve_sources_distributed(solver, comm: Communicator, points, sources, nWalk
     source scored by the same walks, the walk ranges sharded as in solve_distributed.
     Returns (u [S, N] float32, SolveStats with [S, N] mean / stderr, timing dict) on
     every rank, bitwise those of a one-GPU solve_sources."""
-    from .solvers.WoStSolver import SolveStats, _stats_of_multi
+    from .solvers.channels import stats_of_channels
 
     if any(hasattr(s, "charges") for s in sources):
         raise NotImplementedError("solve_sources_distributed takes source fields; for point sources call "
@@ -454,18 +452,16 @@ def solve_sources_distributed(solver, comm: Communicator, points, sources, nWalk
                                   "wost_solve_distributed through the C ABI")
     p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 2))
     fields = solver.source_fields(sources)
-    stats, steps, lsteps, kms, tms = [], 0, 0, 0.0, 0.0
+    rows, steps, lsteps, kms, tms = [], 0, 0, 0.0, 0.0
     for c0 in range(0, len(fields), _lib.WOST_MAX_SOURCES):
         with solver.sources_installed(fields[c0:c0 + _lib.WOST_MAX_SOURCES]):
             sums, timing = _distributed_sums(solver, comm, p, nWalks, maxSteps, eps, seed)
-        stats.extend(_stats_of_multi(sums, int(nWalks)))
+        rows.append(sums)
         steps += timing["all_steps"]
         lsteps += timing["total_steps"]
         kms += timing["walk_kernel_ms"]
         tms += timing["total_ms"]
     timing = dict(timing, all_steps=steps, total_steps=lsteps, walk_kernel_ms=kms, total_ms=tms)
     solver.last_timing = timing
-    u = np.stack([st.mean.astype(np.float32) for st in stats])
-    return u, SolveStats(mean=np.stack([st.mean for st in stats]), stderr=np.stack([st.stderr for st in stats]),
-                         mean_steps=stats[0].mean_steps, walks=int(nWalks), total_steps=steps, kernel_ms=kms,
-                         total_ms=tms), timing
+    st = stats_of_channels(rows, nWalks, steps, kms, tms)
+    return st.mean.astype(np.float32), st, timing

@@ -182,8 +182,8 @@ def solve_key(seed: int, eps: float, max_steps: int, points) -> np.ndarray:
 
     p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 2))
     key = np.zeros(6, np.float64)
-    _lib.check(_lib.lib.wost_dist_solve_key(int(seed) & (2**64 - 1), float(eps), int(max_steps), _lib.fptr(p),
-                                            p.shape[0], _lib.dptr(key)), "wost_dist_solve_key")
+    _lib.check(_lib.lib.wost_dist_solve_key(_lib.seed64(seed), float(eps), int(max_steps), _lib.fptr(p), p.shape[0],
+                                            _lib.dptr(key)), "wost_dist_solve_key")
     return key
 
 

@@ -26,11 +26,14 @@ import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
 from .. import _lib
 from ..fields import Field, as_field, const, detach
+from .channels import (Launch, SolveStats, _model_chunks, _stats_of_multi, charge_lists, plan_launches,  # noqa: F401
+                       point_source_chunks, source_chunks, stats_from_sums, stats_of_channels)
 
 
 def _is_torch(a) -> bool:
@@ -54,6 +57,30 @@ def _points_np(a) -> np.ndarray:
     return p
 
 
+def _walk_count(nWalks) -> int:
+    nWalks = int(nWalks)
+    if nWalks < 1:
+        raise ValueError("nWalks must be >= 1")
+    return nWalks
+
+
+def _wavenumbers_of(k) -> np.ndarray:
+    kk = np.atleast_1d(np.asarray(k, np.float64)).ravel()
+    if kk.size < 1:
+        raise ValueError("k must hold at least one wavenumber")
+    return kk
+
+
+class _Run(NamedTuple):
+    """What WostSolver_2D._run_plan returns."""
+
+    sums: np.ndarray          # [M, K, S, N, 3] float64
+    vals: np.ndarray | None   # [M, K, S, N, W] float32
+    steps: np.ndarray | None  # [N, W] uint32
+    timings: list             # timing() of every launch
+    rows: list                # point rows [N, 2C+1] of every launch
+
+
 def _field_or_none(f, what: str):
     if f is None:
         return None
@@ -67,28 +94,6 @@ def _bounds_of(dxy: np.ndarray, nxy) -> list:
     allp = dxy if nxy is None else np.concatenate([dxy, nxy])
     return [[float(allp[:, 0].min()), float(allp[:, 0].max())],
             [float(allp[:, 1].min()), float(allp[:, 1].max())]]
-
-
-@dataclass
-class SolveStats:
-    """Per-point Monte-Carlo statistics of one solve."""
-
-    mean: np.ndarray        # [N] float64: sum / nWalks
-    stderr: np.ndarray      # [N] float64: sample std / sqrt(nWalks)
-    mean_steps: np.ndarray  # [N] float64
-    walks: int              # walks per point
-    total_steps: int
-    kernel_ms: float        # walk-kernel time (HIP events)
-    total_ms: float         # device time of the whole solve
-
-
-def stats_from_sums(sums: np.ndarray, n_walks: int, total_steps=None, kernel_ms=0.0, total_ms=0.0) -> SolveStats:
-    s, q, st = sums[:, 0], sums[:, 1], sums[:, 2]
-    mean = s / n_walks
-    var = np.maximum(q / n_walks - mean * mean, 0.0) * (n_walks / max(n_walks - 1, 1))
-    return SolveStats(mean=mean, stderr=np.sqrt(var / n_walks), mean_steps=st / n_walks, walks=n_walks,
-                      total_steps=int(st.sum()) if total_steps is None else int(total_steps),
-                      kernel_ms=float(kernel_ms), total_ms=float(total_ms))
 
 
 @dataclass
@@ -250,27 +255,18 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
     if compat not in _lib.COMPAT:
         raise ValueError(f"compat must be one of {sorted(_lib.COMPAT)}")
     prob, keep = _problem(dxy, nxy, g, f, s, a, compat, 0, sigma_bar)
-    packed = [_lib.make_field(conv(x, "source")) for x in (sources or [])]
-    arr = (ctypes.POINTER(_lib.WostField) * max(1, len(packed)))(*[ctypes.pointer(wf) for wf, _ in packed])
+    arr, keep_s = _lib.pack_fields([conv(x, "source") for x in (sources or [])])
+    n_src = len(sources or [])
     n = ctypes.c_int64(0)
-    call = lambda buf, cap: _lib.lib.wost_kernel_source_channels(ctypes.byref(prob), arr, len(packed),
-                                                                  int(n_wavenumbers), buf, cap, ctypes.byref(n))
+    call = lambda buf, cap: _lib.lib.wost_kernel_source_channels(ctypes.byref(prob), arr, n_src, int(n_wavenumbers),
+                                                                  buf, cap, ctypes.byref(n))
     if models is not None:
-        marr = (_lib.WostModel * max(1, len(models)))()
-        for m, (sg, al) in enumerate(models):
-            ms, ma = conv(sg, f"models[{m}].sigma"), conv(al, f"models[{m}].alpha", is_alpha=True)
-            if ma is not None and ma.is_constant():
-                ma = detach(ma)
-            for name, fld in (("sigma", ms), ("alpha", ma)):
-                wf, k = _lib.make_field(fld)
-                keep.append(k)
-                setattr(marr[m], name, ctypes.pointer(wf) if wf is not None else None)
-        call = lambda buf, cap: _lib.lib.wost_kernel_source_models(ctypes.byref(prob), marr, len(models), arr,
-                                                                    len(packed), int(n_wavenumbers), buf, cap,
-                                                                    ctypes.byref(n))
+        marr, keep_m = _lib.pack_models(_model_fields(conv, models))
+        call = lambda buf, cap: _lib.lib.wost_kernel_source_models(ctypes.byref(prob), marr, len(models), arr, n_src,
+                                                                    int(n_wavenumbers), buf, cap, ctypes.byref(n))
     if point_list:
         marr, nm = (None, 0) if models is None else (marr, len(models))
-        call = lambda buf, cap: _lib.lib.wost_kernel_source_point_list(ctypes.byref(prob), marr, nm, arr, len(packed),
+        call = lambda buf, cap: _lib.lib.wost_kernel_source_point_list(ctypes.byref(prob), marr, nm, arr, n_src,
                                                                         int(n_wavenumbers), buf, cap, ctypes.byref(n))
     if options:
         names = (ctypes.c_char_p * len(options))(*[k.encode() for k in options])
@@ -349,6 +345,24 @@ def pack_point_charges(charges):
 def is_point_source(src) -> bool:
     """A survey.PointSource-like source (an object with a ``charges`` list)."""
     return hasattr(src, "charges")
+
+
+def _model_fields(conv, models) -> list:
+    """WostSolver_2D.model_fields with the converter ``conv``."""
+    out = []
+    for m, pair in enumerate(models):
+        try:
+            sg, al = pair
+        except (TypeError, ValueError):
+            raise TypeError(f"models[{m}] must be a (sigma, alpha) pair") from None
+        if sg is None and al is None:
+            raise ValueError(f"models[{m}] has neither sigma nor alpha")
+        s = conv(sg, f"models[{m}].sigma")
+        a = conv(al, f"models[{m}].alpha", is_alpha=True)
+        if a is not None and a.is_constant():
+            a = detach(a)
+        out.append((s, a))
+    return out
 
 
 class _Converter:
@@ -483,7 +497,7 @@ class WostSolver_2D:
         nb = int(block_end) - int(block_begin)
         bs = np.zeros((max(nb, 0), 3), np.float64)
         _lib.check(_lib.lib.wost_solve(self._h, _lib.fptr(p), p.shape[0], int(nWalks), int(block_begin),
-                                       int(block_end), int(maxSteps), float(eps), int(seed) & (2**64 - 1),
+                                       int(block_end), int(maxSteps), float(eps), _lib.seed64(seed),
                                        _lib.dptr(bs), None, _lib.fptr(walk_values), _lib.u32ptr(walk_steps)),
                    "WostSolver_2D.solve")
         self.last_timing = self.timing()
@@ -507,21 +521,20 @@ class WostSolver_2D:
         p = _points_np(solvePoints)
         n = p.shape[0]
         ids, rows, nbr = _range_layout(n, point_ids, walk_begin, walk_end)
-        ns = ctypes.c_int32(1)   # values per walk: sources x wavenumbers
-        _lib.check(_lib.lib.wost_num_channels(self._h, ctypes.byref(ns)), "wost_num_channels")
-        for a, dt, size in ((walk_values, np.float32, ns.value), (walk_steps, np.uint32, 1)):
+        ns = self.num_channels()   # values per walk: models x wavenumbers x sources
+        for a, dt, size in ((walk_values, np.float32, ns), (walk_steps, np.uint32, 1)):
             if a is not None and (a.dtype != dt or not a.flags.c_contiguous or
                                   a.size != rows * max(int(walk_end) - int(walk_begin), 0) * size):
                 raise ValueError("walk_values / walk_steps: contiguous float32 [rows, walks, C] / uint32 [rows, walks]")
-        bs = np.zeros((rows, max(nbr, 0), 2 * ns.value + 1), np.float64)
+        bs = np.zeros((rows, max(nbr, 0), 2 * ns + 1), np.float64)
         if ids is None:
             rc = _lib.lib.wost_solve_range(self._h, _lib.fptr(p), n, int(nWalks), int(walk_begin), int(walk_end),
-                                           int(maxSteps), float(eps), int(seed) & (2**64 - 1), _lib.dptr(bs), None,
+                                           int(maxSteps), float(eps), _lib.seed64(seed), _lib.dptr(bs), None,
                                            _lib.fptr(walk_values), _lib.u32ptr(walk_steps))
         else:
             rc = _lib.lib.wost_solve_range_points(self._h, _lib.fptr(p), n, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                                   rows, int(nWalks), int(walk_begin), int(walk_end), int(maxSteps),
-                                                  float(eps), int(seed) & (2**64 - 1), _lib.dptr(bs), None,
+                                                  float(eps), _lib.seed64(seed), _lib.dptr(bs), None,
                                                   _lib.fptr(walk_values), _lib.u32ptr(walk_steps))
         _lib.check(rc, "WostSolver_2D.solve_range")
         self.last_timing = self.timing()
@@ -563,7 +576,7 @@ class WostSolver_2D:
         rc = _lib.lib.wost_solve_range_combined(
             self._h, _lib.fptr(p), n, None if ids is None else ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
             rows if ids is not None else 0, int(nWalks), int(walk_begin), int(walk_end), int(maxSteps), float(eps),
-            int(seed) & (2**64 - 1), _lib.dptr(w), L, _lib.dptr(bs), _lib.dptr(point_sums), _lib.dptr(cps))
+            _lib.seed64(seed), _lib.dptr(w), L, _lib.dptr(bs), _lib.dptr(point_sums), _lib.dptr(cps))
         _lib.check(rc, "WostSolver_2D.solve_range_combinations")
         self.last_timing = self.timing()
         return bs
@@ -585,9 +598,7 @@ class WostSolver_2D:
         reduced on the device (``solve_range_combinations``); the point rows are the block
         rows added in block order and are kept in ``last_point_sums`` [N, 2L+1]."""
         p = _points_np(solvePoints)
-        nWalks = int(nWalks)
-        if nWalks < 1:
-            raise ValueError("nWalks must be >= 1")
+        nWalks = _walk_count(nWalks)
         bs = self.solve_range_combinations(p, weights, nWalks, 0, nWalks, maxSteps, eps, seed)
         n, nbr, row = bs.shape
         sums = np.zeros((n, row), np.float64)
@@ -614,38 +625,16 @@ class WostSolver_2D:
         wavenumbers and source are restored afterwards."""
         from ..survey import difference_weights
 
-        mods = self.model_fields(models)
-        if len(mods) < 2:
-            raise ValueError("solve_models_differences needs at least two models")
-        if sources is not None and any(is_point_source(s) for s in sources):
-            raise NotImplementedError("solve_models scores source fields: point sources under several models are "
-                                      "not supported")
-        fields = None if sources is None else self.source_fields(sources)
-        kk = None if k is None else np.atleast_1d(np.asarray(k, np.float64)).ravel()
-        if kk is not None and kk.size < 1:
-            raise ValueError("k must hold at least one wavenumber")
+        mods, fields, kk = self._models_request(models, sources, k, 2)
         M, S, K = len(mods), 1 if fields is None else len(fields), 1 if kk is None else kk.size
         cap = _lib.WOST_MAX_SOURCES
         if M * K * S > cap:   # (the (M - 1) K S rows then fit too)
             raise ValueError(f"{M} models x {K} wavenumbers x {S} sources are {M * K * S} channels, more than one "
                              f"launch's {cap}: use solve_models_walks with survey.paired_difference")
         w = difference_weights(M, K, S)
-        saved_k, saved_m = self.wavenumbers, getattr(self, "models", None)
-        self.set_wavenumbers(None)   # (the setters check models x wavenumbers x sources)
-        self.set_models(None)
-        try:
-            with (contextlib.nullcontext() if fields is None else self.sources_installed(fields)):
-                try:
-                    self.set_models(mods)
-                    if kk is not None:
-                        self.set_wavenumbers(kk)
-                    _, st = self.solve_combinations(solvePoints, w, nWalks, maxSteps, eps, seed=seed, return_stats=True)
-                finally:
-                    self.set_wavenumbers(None)
-                    self.set_models(None)
-        finally:
-            self.set_models(saved_m)
-            self.set_wavenumbers(saved_k)
+        with self.channels_installed(fields, mods, kk) as install:
+            install(Launch((0, M), (0, K), (0, S)))
+            _, st = self.solve_combinations(solvePoints, w, nWalks, maxSteps, eps, seed=seed, return_stats=True)
         n = st.mean.shape[1]
         shape = (M - 1,) + ((K,) if k is not None else ()) + ((S,) if sources is not None else ()) + (n,)
         return st.mean.reshape(shape), st.stderr.reshape(shape)
@@ -804,9 +793,7 @@ class WostSolver_2D:
         """
         p = _points_np(solvePoints)
         n = p.shape[0]
-        nWalks = int(nWalks)
-        if nWalks < 1:
-            raise ValueError("nWalks must be >= 1")
+        nWalks = _walk_count(nWalks)
         sums = np.zeros((n, 3), np.float64)
         if return_history:
             # the recorder keeps maxSteps + 1 records per walk on the host: refuse sizes the
@@ -822,13 +809,13 @@ class WostSolver_2D:
             stride = int(maxSteps) + 1
             rec = np.empty((n * nWalks, stride, _lib.REC_FLOATS), np.float32)
             _lib.check(_lib.lib.wost_solve_history(self._h, _lib.fptr(p), n, nWalks, int(maxSteps), float(eps),
-                                                   int(seed) & (2**64 - 1), _lib.dptr(sums), _lib.fptr(wv),
+                                                   _lib.seed64(seed), _lib.dptr(sums), _lib.fptr(wv),
                                                    _lib.u32ptr(ws), _lib.fptr(rec)),
                        "WostSolver_2D.solve")
         else:
             nb = self.num_blocks(n, nWalks)
             _lib.check(_lib.lib.wost_solve(self._h, _lib.addr(p), n, nWalks, 0, nb, int(maxSteps), float(eps),
-                                           int(seed) & (2**64 - 1), None, _lib.addr(sums), None, None),
+                                           _lib.seed64(seed), None, _lib.addr(sums), None, None),
                        "WostSolver_2D.solve")
         self.last_timing = self.timing()
         self.last_point_sums = sums
@@ -848,14 +835,12 @@ class WostSolver_2D:
         i * nWalks + j, as in return_history)."""
         p = _points_np(solvePoints)
         n = p.shape[0]
-        nWalks = int(nWalks)
-        if nWalks < 1:
-            raise ValueError("nWalks must be >= 1")
+        nWalks = _walk_count(nWalks)
         wv = np.empty(n * nWalks, np.float32)
         ws = np.empty(n * nWalks, np.uint32)
         nb = self.num_blocks(n, nWalks)
         _lib.check(_lib.lib.wost_solve(self._h, _lib.fptr(p), n, nWalks, 0, nb, int(maxSteps), float(eps),
-                                       int(seed) & (2**64 - 1), None, None, _lib.fptr(wv), _lib.u32ptr(ws)),
+                                       _lib.seed64(seed), None, None, _lib.fptr(wv), _lib.u32ptr(ws)),
                    "WostSolver_2D.solve_walks")
         self.last_timing = self.timing()
         return wv.reshape(n, nWalks), ws.reshape(n, nWalks)
@@ -874,8 +859,7 @@ class WostSolver_2D:
         the block; the solver's own (single) source is restored afterwards."""
         if not 1 <= len(fields) <= _lib.WOST_MAX_SOURCES:
             raise ValueError(f"1..{_lib.WOST_MAX_SOURCES} sources per launch, got {len(fields)}")
-        packed = [_lib.make_field(f) for f in fields]
-        arr = (ctypes.POINTER(_lib.WostField) * len(fields))(*[ctypes.pointer(wf) for wf, _ in packed])
+        arr, keep = _lib.pack_fields(fields)
         _lib.check(_lib.lib.wost_set_sources(self._h, arr, len(fields)), "WostSolver_2D.solve_sources")
         try:
             yield len(fields)
@@ -893,40 +877,149 @@ class WostSolver_2D:
         fields = self.source_fields(sources)
         for c0 in range(0, len(fields), _lib.WOST_MAX_SOURCES):
             chunk = fields[c0:c0 + _lib.WOST_MAX_SOURCES]
-            packed = [_lib.make_field(f) for f in chunk]
-            arr = (ctypes.POINTER(_lib.WostField) * len(chunk))(*[ctypes.pointer(wf) for wf, _ in packed])
+            arr, keep = _lib.pack_fields(chunk)
             _lib.check(_lib.lib.wost_prepare_sources(self._h, arr, len(chunk), int(n_points)),
                        "WostSolver_2D.prepare_sources")
 
-    def _solve_sources(self, solvePoints, sources, nWalks, maxSteps, eps, seed, want_walks):
-        p = _points_np(solvePoints)
+    # ---- channel batching: one launch, one installer, one runner ----------------
+    def _launch(self, p, nWalks, n_blocks, C, maxSteps, eps, seed, want_walks, what):
+        """All walks of the points ``p`` with the C channels the handle has installed
+        (wost_solve_multi; the package's only call of it): (point rows [N, 2C+1], per-walk values
+        float32 [N * nWalks * C] or None, steps uint32 [N * nWalks] or None, ``timing()``)."""
         n = p.shape[0]
-        nWalks = int(nWalks)
-        if nWalks < 1:
-            raise ValueError("nWalks must be >= 1")
-        fields = self.source_fields(sources)
+        rows = np.zeros((n, 2 * C + 1), np.float64)
+        wv = np.empty(n * nWalks * C, np.float32) if want_walks else None
+        ws = np.empty(n * nWalks, np.uint32) if want_walks else None
+        _lib.check(_lib.lib.wost_solve_multi(self._h, _lib.fptr(p), n, nWalks, 0, n_blocks, int(maxSteps), float(eps),
+                                             _lib.seed64(seed), None, _lib.dptr(rows), _lib.fptr(wv), _lib.u32ptr(ws)),
+                   what)
+        return rows, wv, ws, self.timing()
+
+    @contextlib.contextmanager
+    def channels_installed(self, fields=None, models=None, k=None):
+        """Bring the handle to channel sets of these axes and back: ``fields`` (source fields),
+        ``models`` (model_fields) and ``k`` (wavenumbers), each ``None`` when the solve has no
+        such axis. Yields ``install(launch, expect=None, mismatch=None)``, which installs a
+        channels.Launch's slices: its source run (``fields[s0:s1]``, or the launch's point
+        charges), then its models, then its wavenumbers; with ``expect`` it then raises
+        ``mismatch(launch)`` unless ``num_channels() == expect``.
+
+        On entry the solver's wavenumbers are cleared if the solve has wavenumbers or models,
+        and its models if it has models: the setters check models x wavenumbers x sources. A
+        solve of sources alone leaves both as they are. A source run stays installed for every
+        following launch of the same run, and so do the models while run and models stay. When
+        they change, and on exit, what was cleared on entry is cleared again, then the run's
+        own source (sources_installed, point_sources_installed) comes back; on exit the
+        solver's models, then its wavenumbers are set again."""
+        clear_m = models is not None
+        clear_k = clear_m or k is not None
+        saved_k, saved_m = self.wavenumbers, self.models
+
+        def clear():
+            if clear_k:
+                self.set_wavenumbers(None)
+            if clear_m:
+                self.set_models(None)
+
+        at = [None, None]   # the installed launch's source run and models
+
+        def install(launch, expect=None, mismatch=None):
+            if at != [launch.s, launch.m]:
+                under.close()
+                if at[0] != launch.s:
+                    run.close()
+                    at[:] = launch.s, None
+                    if launch.charges is not None:
+                        run.enter_context(self.point_sources_installed(launch.charges))
+                    elif fields is not None:
+                        run.enter_context(self.sources_installed(fields[slice(*launch.s)]))
+                at[1] = launch.m
+                under.callback(clear)
+                if models is not None:
+                    self.set_models(models[slice(*launch.m)])
+            if k is not None:
+                self.set_wavenumbers(k[slice(*launch.k)])
+            if expect is not None and self.num_channels() != expect:
+                raise mismatch(launch)
+
+        clear()
+        try:
+            with contextlib.ExitStack() as run, contextlib.ExitStack() as under:   # (under closes first)
+                yield install
+        finally:
+            if clear_m:
+                self.set_models(saved_m)
+            if clear_k:
+                self.set_wavenumbers(saved_k)
+
+    def _run_plan(self, plan, shape, p, nWalks, maxSteps, eps, seed, want_walks, what, *, fields=None, models=None,
+                  k=None, mismatch=None, sum_timings=True):
+        """Run the launches ``plan`` (channels.plan_launches) of a request of ``shape`` = (M, K, S)
+        channels and scatter their rows: a _Run of ``sums`` [M, K, S, N, 3] (sum, sum^2, steps),
+        ``vals`` float32 [M, K, S, N, W] and ``steps`` uint32 [N, W] (``want_walks``; the paths do
+        not depend on the channel, the steps are the last launch's), the launches' own
+        ``timings`` and their point ``rows``. ``channels_installed`` moves the handle from
+        launch to launch, and ``wavenumbers``, ``models`` and ``point_sources`` are afterwards
+        what they were, whether the solve succeeded or not.
+
+        What the callers differ in, on purpose:
+        * solve_sources and solve_point_sources (no ``k``, no ``models``) leave the solver's
+          wavenumbers and models installed and refuse -- ``mismatch``, a ValueError -- a handle
+          that then scores more than one channel per source. The others clear them first and
+          take a wrong channel count for a bug (RuntimeError).
+        * ``sum_timings``: solve_wavenumbers and solve_models sum _SUMMED_TIMINGS over the
+          launches into ``last_timing`` (the launch shape stays the last launch's);
+          solve_sources and solve_point_sources keep the last launch's.
+        * ``total_steps`` of the stats is the caller's: the first launch's step column
+          (solve_sources, solve_point_sources, solve_wavenumbers: one walk set's, like
+          ``mean_steps``) or the summed timing's (solve_models: every walk set that ran).
+        Every launch gets the same seed, so that the launches share their walks."""
+        M, K, S = shape
+        n = p.shape[0]
         nb = self.num_blocks(n, nWalks)
-        sums, vals, steps = [], [], None
-        for c0 in range(0, len(fields), _lib.WOST_MAX_SOURCES):
-            with self.sources_installed(fields[c0:c0 + _lib.WOST_MAX_SOURCES]) as S:
-                if self.num_channels() != S:   # (wost_solve_multi would write rows of 2C+1, values [walks][C])
-                    raise ValueError(f"solve_sources scores one value per source, but the solver scores "
-                                     f"{self.num_channels() // S} channels per source: wavenumbers "
-                                     "(set_wavenumbers) or models (set_models) are set. Use "
-                                     "solve_wavenumbers(points, k, sources=...) or solve_models(points, models, "
-                                     "sources=...), or clear them with set_wavenumbers(None) / set_models(None)")
-                s = np.zeros((n, 2 * S + 1), np.float64)
-                wv = np.empty(n * nWalks * S, np.float32) if want_walks else None
-                ws = np.empty(n * nWalks, np.uint32) if want_walks else None
-                _lib.check(_lib.lib.wost_solve_multi(self._h, _lib.fptr(p), n, nWalks, 0, nb, int(maxSteps),
-                                                     float(eps), int(seed) & (2**64 - 1), None, _lib.dptr(s),
-                                                     _lib.fptr(wv), _lib.u32ptr(ws)), "WostSolver_2D.solve_sources")
-                self.last_timing = self.timing()
-            sums.append(s)
-            if want_walks:
-                vals.append(wv.reshape(n, nWalks, S).transpose(2, 0, 1))
-                steps = ws.reshape(n, nWalks)
-        return sums, vals, steps
+        run = _Run(np.zeros((M, K, S, n, 3), np.float64),
+                   np.empty((M, K, S, n, nWalks), np.float32) if want_walks else None, None, [], [])
+        if mismatch is None:
+            mismatch = lambda ln: RuntimeError(f"the handle scores {self.num_channels()} channels, expected {ln.channels}")
+        with self.channels_installed(fields, models, k) as install:
+            for ln in plan:
+                (m0, m1), (k0, k1), (s0, s1) = ln.m, ln.k, ln.s
+                C = ln.channels
+                install(ln, C, mismatch)   # (the buffers below hold C values per walk)
+                rows, wv, ws, t = self._launch(p, nWalks, nb, C, maxSteps, eps, seed, want_walks, what)
+                run.timings.append(dict(t))
+                run.rows.append(rows)
+                if sum_timings and len(run.timings) > 1:
+                    for key in _SUMMED_TIMINGS:
+                        t[key] += self.last_timing[key]
+                self.last_timing = t
+                box = run.sums[m0:m1, k0:k1, s0:s1]
+                box[..., :2] = rows[:, :2 * C].reshape((n,) + ln.shape + (2,)).transpose(1, 2, 3, 0, 4)
+                box[..., 2] = rows[:, -1]
+                if want_walks:
+                    run.vals[m0:m1, k0:k1, s0:s1] = wv.reshape((n, nWalks) + ln.shape).transpose(2, 3, 4, 0, 1)
+                    run = run._replace(steps=ws.reshape(n, nWalks))
+        return run
+
+    def _source_stats(self, run, nWalks, return_stats):
+        """solve_sources' and solve_point_sources' result: u float32 [S, N] and the stacked stats."""
+        st = stats_of_channels(run.rows, nWalks)
+        st.kernel_ms, st.total_ms = self.last_timing["walk_kernel_ms"], self.last_timing["total_ms"]
+        u = st.mean.astype(np.float32)
+        return (u, st) if return_stats else u
+
+    def _run_sources(self, solvePoints, sources, nWalks, maxSteps, eps, seed, want_walks):
+        p, nWalks = _points_np(solvePoints), _walk_count(nWalks)
+        fields = self.source_fields(sources)
+        S, cap = len(fields), _lib.WOST_MAX_SOURCES
+        refuse = lambda ln: ValueError(   # (wost_solve_multi would write rows of 2C+1, values [walks][C])
+            f"solve_sources scores one value per source, but the solver scores "
+            f"{self.num_channels() // ln.channels} channels per source: wavenumbers (set_wavenumbers) or models "
+            "(set_models) are set. Use solve_wavenumbers(points, k, sources=...) or solve_models(points, models, "
+            "sources=...), or clear them with set_wavenumbers(None) / set_models(None)")
+        return self._run_plan(plan_launches(1, 1, S, cap, chunks=source_chunks(S, cap)), (1, 1, S), p, nWalks, maxSteps,
+                              eps, seed, want_walks, "WostSolver_2D.solve_sources", fields=fields, mismatch=refuse,
+                              sum_timings=False)
 
     def solve_sources(self, solvePoints, sources, nWalks=1000, maxSteps=1000, eps=1e-4, *, seed: int = 0,
                       return_stats: bool = False):
@@ -938,23 +1031,14 @@ class WostSolver_2D:
         the cost of one solve (16 sources per launch; more are batched in groups).
         Returns float32 [S, N]; with ``return_stats`` also a SolveStats whose mean
         and stderr are [S, N]. The solver's own source is restored afterwards."""
-        sums, _, _ = self._solve_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, False)
-        stats = [st for s in sums for st in _stats_of_multi(s, int(nWalks))]
-        u = np.stack([st.mean.astype(np.float32) for st in stats])
-        if not return_stats:
-            return u
-        t = self.last_timing
-        return u, SolveStats(mean=np.stack([st.mean for st in stats]), stderr=np.stack([st.stderr for st in stats]),
-                             mean_steps=stats[0].mean_steps, walks=stats[0].walks, total_steps=stats[0].total_steps,
-                             kernel_ms=t["walk_kernel_ms"], total_ms=t["total_ms"])
+        run = self._run_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, False)
+        return self._source_stats(run, nWalks, return_stats)
 
     def solve_sources_walks(self, solvePoints, sources, nWalks=1000, maxSteps=1000, eps=1e-4, *, seed: int = 0):
         """Per-walk values of every source, float32 [S, N, nWalks], and the walks'
         step counts, uint32 [N, nWalks] (shared by all sources)."""
-        _, vals, steps = self._solve_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, True)
-        return np.concatenate(vals, axis=0), steps
-
-
+        run = self._run_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, True)
+        return run.vals[0, 0], run.steps
 
     # ---- point sources (DESIGN.md 7b, include/wost.h wost_set_point_sources) ----------------
     def set_point_sources(self, charges=None):
@@ -974,25 +1058,7 @@ class WostSolver_2D:
             return
         arr, n, n_src = pack_point_charges(charges)
         _lib.check(_lib.lib.wost_set_point_sources(self._h, arr, n, n_src), "WostSolver_2D.set_point_sources")
-        self.point_sources = [list(getattr(s, "charges", s)) for s in charges]
-
-    def _point_source_chunks(self, sources, n_k: int = 1):
-        """Runs of sources that fit one launch: at most WOST_MAX_POINT_CHARGES charges and
-        WOST_MAX_SOURCES // n_k sources."""
-        lists = [list(getattr(s, "charges", s)) for s in sources]
-        s_max = max(1, _lib.WOST_MAX_SOURCES // max(1, n_k))
-        chunks, cur, cnt = [], [], 0
-        for lst in lists:
-            if len(lst) > _lib.WOST_MAX_POINT_CHARGES:
-                raise ValueError(f"a point source of {len(lst)} charges exceeds {_lib.WOST_MAX_POINT_CHARGES} per launch")
-            if cur and (cnt + len(lst) > _lib.WOST_MAX_POINT_CHARGES or len(cur) >= s_max):
-                chunks.append(cur)
-                cur, cnt = [], 0
-            cur.append(lst)
-            cnt += len(lst)
-        if cur:
-            chunks.append(cur)
-        return chunks
+        self.point_sources = charge_lists(charges)
 
     @contextlib.contextmanager
     def point_sources_installed(self, sources):
@@ -1005,53 +1071,30 @@ class WostSolver_2D:
         finally:
             self.set_point_sources(saved)
 
-    def _solve_point_sources(self, solvePoints, sources, nWalks, maxSteps, eps, seed, want_walks):
-        p = _points_np(solvePoints)
-        n = p.shape[0]
-        nWalks = int(nWalks)
-        if nWalks < 1:
-            raise ValueError("nWalks must be >= 1")
-        nb = self.num_blocks(n, nWalks)
-        sums, vals, steps = [], [], None
-        for chunk in self._point_source_chunks(sources, 1 if self.wavenumbers is None else len(self.wavenumbers)):
-            with self.point_sources_installed(chunk) as S:
-                if self.num_channels() != S:
-                    raise ValueError("solve_point_sources scores one value per source, but the solver has wavenumbers "
-                                     "or models set: use solve_wavenumbers(points, k, sources=...), or clear them "
-                                     "with set_wavenumbers(None) / set_models(None)")
-                s = np.zeros((n, 2 * S + 1), np.float64)
-                wv = np.empty(n * nWalks * S, np.float32) if want_walks else None
-                ws = np.empty(n * nWalks, np.uint32) if want_walks else None
-                _lib.check(_lib.lib.wost_solve_multi(self._h, _lib.fptr(p), n, nWalks, 0, nb, int(maxSteps),
-                                                     float(eps), int(seed) & (2**64 - 1), None, _lib.dptr(s),
-                                                     _lib.fptr(wv), _lib.u32ptr(ws)), "WostSolver_2D.solve_point_sources")
-                self.last_timing = self.timing()
-            sums.append(s)
-            if want_walks:
-                vals.append(wv.reshape(n, nWalks, S).transpose(2, 0, 1))
-                steps = ws.reshape(n, nWalks)
-        return sums, vals, steps
+    def _run_point_sources(self, solvePoints, sources, nWalks, maxSteps, eps, seed, want_walks):
+        p, nWalks = _points_np(solvePoints), _walk_count(nWalks)
+        cap, n_k = _lib.WOST_MAX_SOURCES, 1 if self.wavenumbers is None else len(self.wavenumbers)
+        runs = point_source_chunks(charge_lists(sources), cap // n_k, _lib.WOST_MAX_POINT_CHARGES)
+        refuse = lambda ln: ValueError(
+            "solve_point_sources scores one value per source, but the solver has wavenumbers or models set: use "
+            "solve_wavenumbers(points, k, sources=...), or clear them with set_wavenumbers(None) / set_models(None)")
+        S = sum(len(r) for r in runs)
+        return self._run_plan(plan_launches(1, 1, S, cap, runs), (1, 1, S), p, nWalks, maxSteps, eps, seed, want_walks,
+                              "WostSolver_2D.solve_point_sources", mismatch=refuse, sum_timings=False)
 
     def solve_point_sources(self, solvePoints, sources, nWalks=1000, maxSteps=1000, eps=1e-4, *, seed: int = 0,
                             return_stats: bool = False):
         """solve_sources for point sources: u[k] is the solve with the charges of
         ``sources[k]`` alone, all scored by the same walks, bit for bit. Returns float32
         [S, N]; with ``return_stats`` also a SolveStats whose mean and stderr are [S, N]."""
-        sums, _, _ = self._solve_point_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, False)
-        stats = [st for s in sums for st in _stats_of_multi(s, int(nWalks))]
-        u = np.stack([st.mean.astype(np.float32) for st in stats])
-        if not return_stats:
-            return u
-        t = self.last_timing
-        return u, SolveStats(mean=np.stack([st.mean for st in stats]), stderr=np.stack([st.stderr for st in stats]),
-                             mean_steps=stats[0].mean_steps, walks=stats[0].walks, total_steps=stats[0].total_steps,
-                             kernel_ms=t["walk_kernel_ms"], total_ms=t["total_ms"])
+        run = self._run_point_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, False)
+        return self._source_stats(run, nWalks, return_stats)
 
     def solve_point_sources_walks(self, solvePoints, sources, nWalks=1000, maxSteps=1000, eps=1e-4, *, seed: int = 0):
         """Per-walk values of every point source, float32 [S, N, nWalks], and the walks' step
         counts, uint32 [N, nWalks]."""
-        _, vals, steps = self._solve_point_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, True)
-        return np.concatenate(vals, axis=0), steps
+        run = self._run_point_sources(solvePoints, sources, nWalks, maxSteps, eps, seed, True)
+        return run.vals[0, 0], run.steps
 
     # ---- 2.5-D wavenumber batching (DESIGN.md, include/wost.h wost_set_wavenumbers) ---------
     def set_wavenumbers(self, k=None):
@@ -1075,18 +1118,9 @@ class WostSolver_2D:
         _lib.check(_lib.lib.wost_num_channels(self._h, ctypes.byref(n)), "wost_num_channels")
         return int(n.value)
 
-    def _solve_channels(self, solvePoints, k, sources, nWalks, maxSteps, eps, seed, want_walks):
-        """One launch per (source chunk, wavenumber chunk) of at most WOST_MAX_SOURCES
-        channels: rows [Kc][Sc] of point sums [N, 3] and (want_walks) per-walk values
-        [Kc, Sc, N, W]; the solver's wavenumbers and source are restored afterwards."""
-        p = _points_np(solvePoints)
-        n = p.shape[0]
-        nWalks = int(nWalks)
-        if nWalks < 1:
-            raise ValueError("nWalks must be >= 1")
-        kk = np.atleast_1d(np.asarray(k, np.float64)).ravel()
-        if kk.size < 1:
-            raise ValueError("k must hold at least one wavenumber")
+    def _run_wavenumbers(self, solvePoints, k, sources, nWalks, maxSteps, eps, seed, want_walks):
+        p, nWalks = _points_np(solvePoints), _walk_count(nWalks)
+        kk = _wavenumbers_of(k)
         if self.num_models:   # (wost_solve_multi would write rows of 2C+1 with the models' channels)
             raise ValueError(f"solve_wavenumbers scores one value per wavenumber and source, but the solver has "
                              f"{self.num_models} models set (set_models): use solve_models(points, models, k=..., "
@@ -1096,61 +1130,12 @@ class WostSolver_2D:
         if sources is not None and not points and any(is_point_source(s) for s in sources):
             raise ValueError("sources mixes point sources and fields: one kind per solve")
         fields = None if sources is None or points else self.source_fields(sources)
-        S = 1 if sources is None else len(sources)
-        K = kk.size
-        nb = self.num_blocks(n, nWalks)
-        s_chunk = min(S, _lib.WOST_MAX_SOURCES)
-        k_chunk = max(1, _lib.WOST_MAX_SOURCES // s_chunk)
-        if points:   # source runs of at most WOST_MAX_POINT_CHARGES charges, then as many wavenumbers as fit
-            runs, s0 = [], 0
-            for chunk in self._point_source_chunks(sources, 1):
-                runs.append((s0, s0 + len(chunk), chunk))
-                s0 += len(chunk)
-        else:
-            runs = [(s0, min(S, s0 + s_chunk), None) for s0 in range(0, S, s_chunk)]
-        sums = np.zeros((K, S, n, 3), np.float64)
-        vals = np.empty((K, S, n, nWalks), np.float32) if want_walks else None
-        steps = None
-        total = None   # the launches' timings summed (the launch shape: the last launch's)
-        saved = self.wavenumbers
-        self.set_wavenumbers(None)   # (wost_set_sources checks sources x wavenumbers)
-        try:
-            for s0, s1, chunk in runs:
-                ctx = (self.point_sources_installed(chunk) if points else contextlib.nullcontext() if fields is None
-                       else self.sources_installed(fields[s0:s1]))
-                if points:
-                    k_chunk = max(1, _lib.WOST_MAX_SOURCES // (s1 - s0))
-                with ctx:
-                    try:
-                        for k0 in range(0, K, k_chunk):
-                            k1 = min(K, k0 + k_chunk)
-                            self.set_wavenumbers(kk[k0:k1])
-                            C = (k1 - k0) * (s1 - s0)
-                            if self.num_channels() != C:   # (the buffers below hold C values per walk)
-                                raise RuntimeError(f"the handle scores {self.num_channels()} channels, expected {C}")
-                            rows = np.zeros((n, 2 * C + 1), np.float64)
-                            wv = np.empty(n * nWalks * C, np.float32) if want_walks else None
-                            ws = np.empty(n * nWalks, np.uint32) if want_walks else None
-                            _lib.check(_lib.lib.wost_solve_multi(self._h, _lib.fptr(p), n, nWalks, 0, nb, int(maxSteps),
-                                                                 float(eps), int(seed) & (2**64 - 1), None,
-                                                                 _lib.dptr(rows), _lib.fptr(wv), _lib.u32ptr(ws)),
-                                       "WostSolver_2D.solve_wavenumbers")
-                            t = self.timing()
-                            if total is not None:
-                                for key in _SUMMED_TIMINGS:
-                                    t[key] += total[key]
-                            self.last_timing = total = t
-                            r = rows[:, :2 * C].reshape(n, k1 - k0, s1 - s0, 2)
-                            sums[k0:k1, s0:s1, :, :2] = r.transpose(1, 2, 0, 3)
-                            sums[k0:k1, s0:s1, :, 2] = rows[:, -1]
-                            if want_walks:
-                                vals[k0:k1, s0:s1] = wv.reshape(n, nWalks, k1 - k0, s1 - s0).transpose(2, 3, 0, 1)
-                                steps = ws.reshape(n, nWalks)
-                    finally:
-                        self.set_wavenumbers(None)
-        finally:
-            self.set_wavenumbers(saved)
-        return sums, vals, steps
+        S, cap = 1 if sources is None else len(sources), _lib.WOST_MAX_SOURCES
+        # point sources: runs of at most WOST_MAX_POINT_CHARGES charges, then as many wavenumbers as fit
+        runs = point_source_chunks(charge_lists(sources), cap, _lib.WOST_MAX_POINT_CHARGES) if points else None
+        plan = plan_launches(1, kk.size, S, cap, runs, None if points else source_chunks(S, cap))
+        return self._run_plan(plan, (1, kk.size, S), p, nWalks, maxSteps, eps, seed, want_walks,
+                              "WostSolver_2D.solve_wavenumbers", fields=fields, k=kk)
 
     def solve_wavenumbers(self, solvePoints, k, nWalks=1000, maxSteps=1000, eps=1e-4, *, sources=None,
                           seed: int = 0, return_stats: bool = False):
@@ -1163,7 +1148,7 @@ class WostSolver_2D:
         stderr have that shape. More than WOST_MAX_SOURCES channels are solved in several
         launches, and ``last_timing`` / the stats' kernel_ms and total_ms then sum over them.
         The solver's wavenumbers and source are restored afterwards."""
-        sums, _, _ = self._solve_channels(solvePoints, k, sources, nWalks, maxSteps, eps, seed, False)
+        sums = self._run_wavenumbers(solvePoints, k, sources, nWalks, maxSteps, eps, seed, False).sums[0]
         K, S, n = sums.shape[:3]
         st = stats_from_sums(sums.reshape(K * S * n, 3), int(nWalks))
         shape = (K, n) if sources is None else (K, S, n)
@@ -1181,28 +1166,15 @@ class WostSolver_2D:
         """Per-walk values of every wavenumber (and source), float32 [K, N, nWalks] or
         [K, S, N, nWalks], and the walks' step counts, uint32 [N, nWalks] (shared by all
         channels: the paths do not depend on them)."""
-        _, vals, steps = self._solve_channels(solvePoints, k, sources, nWalks, maxSteps, eps, seed, True)
-        return (vals[:, 0] if sources is None else vals), steps
+        run = self._run_wavenumbers(solvePoints, k, sources, nWalks, maxSteps, eps, seed, True)
+        return (run.vals[0, :, 0] if sources is None else run.vals[0]), run.steps
 
     # ---- shared-path model batching (DESIGN.md 7c, include/wost.h wost_set_models) ----------
     def model_fields(self, models) -> list:
         """The device fields of a list of models, each a ``(sigma, alpha)`` pair of fields,
         numbers or callables (``None``: sigma = 0 / alpha = 1, as the constructor's): a list
         of ``(sigma_field | None, alpha_field | None)``; a constant alpha is detached (Q9)."""
-        out = []
-        for m, pair in enumerate(models):
-            try:
-                sg, al = pair
-            except (TypeError, ValueError):
-                raise TypeError(f"models[{m}] must be a (sigma, alpha) pair") from None
-            if sg is None and al is None:
-                raise ValueError(f"models[{m}] has neither sigma nor alpha")
-            s = self._conv(sg, f"models[{m}].sigma")
-            a = self._conv(al, f"models[{m}].alpha", is_alpha=True)
-            if a is not None and a.is_constant():
-                a = detach(a)
-            out.append((s, a))
-        return out
+        return _model_fields(self._conv, models)
 
     def set_models(self, models=None):
         """Score the conductivity models ``models`` -- ``(sigma, alpha)`` pairs -- with every
@@ -1220,13 +1192,7 @@ class WostSolver_2D:
             _lib.check(_lib.lib.wost_set_models(self._h, None, 0), "WostSolver_2D.set_models")
             self.models = None
             return
-        keep = []
-        arr = (_lib.WostModel * len(fields))()
-        for m, (s, a) in enumerate(fields):
-            for name, fld in (("sigma", s), ("alpha", a)):
-                wf, k = _lib.make_field(fld)
-                keep.append(k)
-                setattr(arr[m], name, ctypes.pointer(wf) if wf is not None else None)
+        arr, keep = _lib.pack_models(fields)
         _lib.check(_lib.lib.wost_set_models(self._h, arr, len(fields)), "WostSolver_2D.set_models")
         self.models = fields
 
@@ -1248,76 +1214,23 @@ class WostSolver_2D:
         finally:
             self.set_models(saved)
 
-    def _solve_models(self, solvePoints, models, sources, k, nWalks, maxSteps, eps, seed, want_walks):
-        """One launch per (model chunk, source chunk, wavenumber chunk) of at most
-        WOST_MAX_SOURCES channels: point sums [M, K, S, N, 3] and (want_walks) per-walk values
-        [M, K, S, N, W]; the solver's models, wavenumbers and source are restored afterwards."""
-        p = _points_np(solvePoints)
-        n = p.shape[0]
-        nWalks = int(nWalks)
-        if nWalks < 1:
-            raise ValueError("nWalks must be >= 1")
+    def _models_request(self, models, sources, k, fewest: int = 1):
+        """(model fields, source fields or None, wavenumbers or None) of a solve_models request."""
         mods = self.model_fields(models)
-        if not mods:
-            raise ValueError("models must hold at least one (sigma, alpha) pair")
+        if len(mods) < fewest:
+            raise ValueError("models must hold at least one (sigma, alpha) pair" if fewest == 1
+                             else "solve_models_differences needs at least two models")
         if sources is not None and any(is_point_source(s) for s in sources):
             raise NotImplementedError("solve_models scores source fields: point sources under several models are "
                                       "not supported")
-        fields = None if sources is None else self.source_fields(sources)
-        kk = None if k is None else np.atleast_1d(np.asarray(k, np.float64)).ravel()
-        if kk is not None and kk.size < 1:
-            raise ValueError("k must hold at least one wavenumber")
-        M, S, K = len(mods), 1 if fields is None else len(fields), 1 if kk is None else kk.size
-        m_chunk, s_chunk, k_chunk = _model_chunks(M, S, K, _lib.WOST_MAX_SOURCES)
-        nb = self.num_blocks(n, nWalks)
-        sums = np.zeros((M, K, S, n, 3), np.float64)
-        vals = np.empty((M, K, S, n, nWalks), np.float32) if want_walks else None
-        steps = None
-        total = None
-        saved_k, saved_m = self.wavenumbers, getattr(self, "models", None)
-        self.set_wavenumbers(None)   # (the setters check models x wavenumbers x sources)
-        self.set_models(None)
-        try:
-            for s0 in range(0, S, s_chunk):
-                s1 = min(S, s0 + s_chunk)
-                with (contextlib.nullcontext() if fields is None else self.sources_installed(fields[s0:s1])):
-                    for m0 in range(0, M, m_chunk):
-                        m1 = min(M, m0 + m_chunk)
-                        try:
-                            self.set_models(mods[m0:m1])
-                            for k0 in range(0, K, k_chunk):
-                                k1 = min(K, k0 + k_chunk)
-                                if kk is not None:
-                                    self.set_wavenumbers(kk[k0:k1])
-                                dm, dk, ds = m1 - m0, k1 - k0, s1 - s0
-                                C = dm * dk * ds
-                                if self.num_channels() != C:   # (the buffers below hold C values per walk)
-                                    raise RuntimeError(f"the handle scores {self.num_channels()} channels, expected {C}")
-                                rows = np.zeros((n, 2 * C + 1), np.float64)
-                                wv = np.empty(n * nWalks * C, np.float32) if want_walks else None
-                                ws = np.empty(n * nWalks, np.uint32) if want_walks else None
-                                _lib.check(_lib.lib.wost_solve_multi(self._h, _lib.fptr(p), n, nWalks, 0, nb,
-                                                                     int(maxSteps), float(eps), int(seed) & (2**64 - 1),
-                                                                     None, _lib.dptr(rows), _lib.fptr(wv),
-                                                                     _lib.u32ptr(ws)), "WostSolver_2D.solve_models")
-                                t = self.timing()
-                                if total is not None:
-                                    for key in _SUMMED_TIMINGS:
-                                        t[key] += total[key]
-                                self.last_timing = total = t
-                                r = rows[:, :2 * C].reshape(n, dm, dk, ds, 2)
-                                sums[m0:m1, k0:k1, s0:s1, :, :2] = r.transpose(1, 2, 3, 0, 4)
-                                sums[m0:m1, k0:k1, s0:s1, :, 2] = rows[:, -1]
-                                if want_walks:
-                                    vals[m0:m1, k0:k1, s0:s1] = wv.reshape(n, nWalks, dm, dk, ds).transpose(2, 3, 4, 0, 1)
-                                    steps = ws.reshape(n, nWalks)
-                        finally:
-                            self.set_wavenumbers(None)
-                            self.set_models(None)
-        finally:
-            self.set_models(saved_m)
-            self.set_wavenumbers(saved_k)
-        return sums, vals, steps
+        return mods, None if sources is None else self.source_fields(sources), None if k is None else _wavenumbers_of(k)
+
+    def _run_models(self, solvePoints, models, sources, k, nWalks, maxSteps, eps, seed, want_walks):
+        p, nWalks = _points_np(solvePoints), _walk_count(nWalks)
+        mods, fields, kk = self._models_request(models, sources, k)
+        shape = len(mods), 1 if kk is None else kk.size, 1 if fields is None else len(fields)
+        return self._run_plan(plan_launches(*shape, _lib.WOST_MAX_SOURCES), shape, p, nWalks, maxSteps, eps, seed,
+                              want_walks, "WostSolver_2D.solve_models", fields=fields, models=mods, k=kk)
 
     def solve_models(self, solvePoints, models, nWalks=1000, maxSteps=1000, eps=1e-4, *, sources=None, k=None,
                      seed: int = 0, return_stats: bool = False):
@@ -1332,7 +1245,7 @@ class WostSolver_2D:
         (``_model_chunks``); every launch is a walk set of its own, ``last_timing`` sums over
         them, and the stats' ``total_steps`` counts every walk set that ran (``mean_steps`` is
         one walk set's). The solver's models, wavenumbers and source are restored afterwards."""
-        sums, _, _ = self._solve_models(solvePoints, models, sources, k, nWalks, maxSteps, eps, seed, False)
+        sums = self._run_models(solvePoints, models, sources, k, nWalks, maxSteps, eps, seed, False).sums
         M, K, S, n = sums.shape[:4]
         st = stats_from_sums(sums.reshape(M * K * S * n, 3), int(nWalks))
         shape = (M,) + ((K,) if k is not None else ()) + ((S,) if sources is not None else ()) + (n,)
@@ -1350,35 +1263,12 @@ class WostSolver_2D:
         """Per-walk values of every model (wavenumber, source), float32 [M, N, nWalks] (or
         [M, K, N, W], [M, S, N, W], [M, K, S, N, W]), and the walks' step counts, uint32
         [N, nWalks], shared by all channels: the paths do not depend on the model."""
-        _, vals, steps = self._solve_models(solvePoints, models, sources, k, nWalks, maxSteps, eps, seed, True)
+        vals, steps = self._run_models(solvePoints, models, sources, k, nWalks, maxSteps, eps, seed, True)[1:3]
         if sources is None:
             vals = vals[:, :, 0]
         if k is None:
             vals = vals[:, 0]
         return vals, steps
-
-
-def _model_chunks(M: int, S: int, K: int, cap: int):
-    """(models, sources, wavenumbers) per launch of solve_models for M x S x K channels at
-    most ``cap`` per launch: the split with the fewest launches -- every launch walks the
-    paths once -- and among those the one that keeps the most models together (then sources),
-    so that a model and its background share a walk set whenever that saves one."""
-    best = None
-    for m in range(1, min(M, cap) + 1):
-        for s in range(1, min(S, cap // m) + 1):
-            k = min(K, cap // (m * s))
-            launches = -(-M // m) * -(-S // s) * -(-K // k)
-            key = (launches, -m, -s)
-            if best is None or key < best[0]:
-                best = (key, (m, s, k))
-    return best[1]
-
-
-def _stats_of_multi(sums: np.ndarray, n_walks: int):
-    """SolveStats of each source from [N, 2S+1] wost_solve_multi rows."""
-    S = (sums.shape[1] - 1) // 2
-    return [stats_from_sums(np.stack([sums[:, 2 * k], sums[:, 2 * k + 1], sums[:, -1]], axis=1), n_walks)
-            for k in range(S)]
 
 
 def _history(rec, wv, ws, n, nWalks, has_neumann, has_source, as_torch):

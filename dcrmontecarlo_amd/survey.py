@@ -742,7 +742,7 @@ def _run_fields_distributed(sc, solvers, srcs, batches, n_walks, seed, comm, rec
     from . import _lib
     from .comm import shard_walk_range
     from .distributed import run_protocol, solve_key
-    from .solvers.WoStSolver import SolveStats, _stats_of_multi
+    from .solvers.channels import stats_of_channels
 
     R, rank = int(comm.n_ranks), int(comm.rank)
     w0, w1 = shard_walk_range(int(n_walks), R, rank)
@@ -800,11 +800,8 @@ def _run_fields_distributed(sc, solvers, srcs, batches, n_walks, seed, comm, rec
                 if phase_ms is not None:
                     for name in ("agree_ms", "gather_ms", "merge_ms"):
                         phase_ms[name] = phase_ms.get(name, 0.0) + ph[name]
-                stats = _stats_of_multi(sums, int(n_walks))
-                st = SolveStats(mean=np.stack([x.mean for x in stats]), stderr=np.stack([x.stderr for x in stats]),
-                                mean_steps=stats[0].mean_steps, walks=int(n_walks), total_steps=int(all_steps),
-                                kernel_ms=float(tm["walk_kernel_ms"]) if tm else 0.0,
-                                total_ms=float(tm["total_ms"]) if tm else 0.0)
+                st = stats_of_channels([sums], n_walks, all_steps, tm["walk_kernel_ms"] if tm else 0.0,
+                                       tm["total_ms"] if tm else 0.0)
                 record(f, g, st, int(tm["total_steps"]) if tm else 0)
     finally:
         stop.set()

@@ -158,30 +158,24 @@ def _one_launch(solver, sources, n_k: int) -> bool:
     """Whether ``sources`` x n_k wavenumbers fit one launch of ``solver`` (point sources: also
     the charges, WOST_MAX_POINT_CHARGES)."""
     from . import _lib
+    from .solvers.channels import charge_lists, point_source_chunks
 
     if len(sources) * n_k > _lib.WOST_MAX_SOURCES:
         return False
-    return not _are_point_sources(sources) or len(solver._point_source_chunks(sources, n_k)) == 1
+    return not _are_point_sources(sources) or len(point_source_chunks(
+        charge_lists(sources), _lib.WOST_MAX_SOURCES // max(1, n_k), _lib.WOST_MAX_POINT_CHARGES)) == 1
 
 
 def _transformed_group_device(solver, pts, sources, kk, ww, n_walks, max_steps, eps, seed):
     """One launch's sum_j w_j u_{k_j} of its sources, reduced on the device: a SolveStats with
     [S, N] mean and stderr. The solver's wavenumbers and source are restored."""
-    points = _are_point_sources(sources)
-    saved = solver.wavenumbers
-    solver.set_wavenumbers(None)   # (the setters check sources x wavenumbers)
-    try:
-        ctx = (solver.point_sources_installed(sources) if points
-               else solver.sources_installed(solver.source_fields(sources)))
-        with ctx:
-            try:
-                solver.set_wavenumbers(kk)
-                _, st = solver.solve_combinations(pts, transform_weights(ww, len(sources)), n_walks, max_steps, eps,
-                                                  seed=seed, return_stats=True)
-            finally:
-                solver.set_wavenumbers(None)
-    finally:
-        solver.set_wavenumbers(saved)
+    from .solvers.channels import Launch
+
+    fields = None if _are_point_sources(sources) else solver.source_fields(sources)
+    with solver.channels_installed(fields, k=kk) as install:   # (point sources come with the launch)
+        install(Launch((0, 1), (0, len(kk)), (0, len(sources)), None if fields is not None else tuple(sources)))
+        _, st = solver.solve_combinations(pts, transform_weights(ww, len(sources)), n_walks, max_steps, eps, seed=seed,
+                                          return_stats=True)
     return st
 
 

@@ -262,6 +262,35 @@ def test_every_channel_equals_its_single_solve(gpu_available):
     s.set_point_sources(None)
 
 
+def test_point_sources_over_two_launches_equal_their_single_solves(gpu_available):
+    """17 point dipoles between neighbouring electrodes, each with a charge on a query point:
+    34 charges (> WOST_MAX_POINT_CHARGES) in 17 sources (> WOST_MAX_SOURCES), so
+    solve_point_sources scores 16 + 1 sources in two launches. Every source's per-walk values,
+    steps, mean and standard error are bit for bit those of its own single solve."""
+    from dcrmontecarlo_amd import survey
+
+    sc, pts, s = _fixed_solver("dd", 2.5)
+    e = np.asarray(sc.points, np.float64)
+    dip = [survey.point_dipole(e[2 + i % 2], e[3 + i % 2], 1.0 + 0.25 * i) for i in range(17)]
+    kw = dict(nWalks=W5, maxSteps=sc.max_steps, eps=sc.eps, seed=SEED)
+    vals, steps = s.solve_point_sources_walks(pts, dip, **kw)
+    u, st = s.solve_point_sources(pts, dip, return_stats=True, **kw)
+    assert vals.shape == (17, 3, W5) and steps.shape == (3, W5) and s.last_timing["jit"] == 1
+    assert u.shape == (17, 3) and st.mean.shape == (17, 3) and st.stderr.shape == (17, 3)
+    assert s.point_sources is None and s.num_channels() == 1   # restored
+    assert np.any(vals[:16] != 0) and np.any(vals[16] != 0)    # both launches scored something
+    for i, d in enumerate(dip):
+        s.set_point_sources([d])
+        v1, s1 = s.solve_walks(pts, **kw)
+        _, st1 = s.solve(pts, return_stats=True, **kw)
+        np.testing.assert_array_equal(steps, s1)
+        np.testing.assert_array_equal(vals[i].view(np.uint32), v1.view(np.uint32))
+        np.testing.assert_array_equal(st.mean[i], st1.mean)
+        np.testing.assert_array_equal(st.stderr[i], st1.stderr)
+        np.testing.assert_array_equal(u[i], st1.mean.astype(np.float32))
+    s.set_point_sources(None)
+
+
 def test_tree_kernel_equals_scan_kernel_with_point_sources(gpu_available):
     """variable_coefficients (a Neumann circle) at 3 wavenumbers, two sources of point charges
     near the circle: the segment-tree kernel's values, sums and steps equal the scan kernel's."""

@@ -67,7 +67,7 @@ class FakeSolver:
         return rows
 
     def solve_sources(self, points, srcs, nWalks, maxSteps, eps, seed, return_stats=True):
-        from dcrmontecarlo_amd.solvers.WoStSolver import SolveStats, _stats_of_multi
+        from dcrmontecarlo_amd.solvers.channels import stats_of_channels
 
         self._sleep()
         with self.sources_installed(srcs):
@@ -75,11 +75,7 @@ class FakeSolver:
         acc = np.zeros((rows.shape[0], rows.shape[2]))
         for b in range(rows.shape[1]):      # block order, from 0.0: the one-GPU point sums
             acc += rows[:, b]
-        stats = _stats_of_multi(acc, int(nWalks))
-        st = SolveStats(mean=np.stack([x.mean for x in stats]), stderr=np.stack([x.stderr for x in stats]),
-                        mean_steps=stats[0].mean_steps, walks=int(nWalks), total_steps=int(acc[:, -1].sum()),
-                        kernel_ms=1.0, total_ms=1.0)
-        return None, st
+        return None, stats_of_channels([acc], nWalks, int(acc[:, -1].sum()), 1.0, 1.0)
 
 
 class LoggedComm:
