@@ -30,6 +30,8 @@ WOST_MAX_SOURCES = 16   # include/wost.h
 WOST_MAX_POINT_CHARGES = 32   # include/wost.h
 WOST_DTREE_MIN_SEGMENTS_DEFAULT = 128   # include/wost.h (wost_set_dirichlet_tree; measured)
 WOST_DTREE_LEAF_DEFAULT = 10
+WOST_TALLY_MAX_CELLS_1D = 1 << 20   # include/wost.h (wost_tally_grid)
+WOST_TALLY_MAX_BYTES = 1 << 30      # include/wost.h (wost_solve_range_tally)
 WOST_TRIG = {"auto": 0, "exact": 1, "fast": 2}   # include/wost.h wost_trig
 WOST_SAMPLER_TABLE_N = 4097
 COMPAT = {"reference": 0, "fixed": 1}
@@ -60,6 +62,11 @@ class WostPointCharge(ctypes.Structure):
 class WostModel(ctypes.Structure):
     """include/wost.h wost_model: a (sigma, alpha) pair; a NULL field follows wost_problem's rules."""
     _fields_ = [("sigma", POINTER(WostField)), ("alpha", POINTER(WostField))]
+
+
+class WostTallyGrid(ctypes.Structure):
+    """include/wost.h wost_tally_grid: nx x ny cells from (x0, y0), widths (dx, dy)."""
+    _fields_ = [("x0", c_float), ("y0", c_float), ("dx", c_float), ("dy", c_float), ("nx", c_int32), ("ny", c_int32)]
 
 
 class WostPolyline(ctypes.Structure):
@@ -163,6 +170,16 @@ def _load():
         "wost_kernel_source_point_list": (c_int32, [POINTER(WostProblem), POINTER(WostModel), c_int32,
                                                     POINTER(POINTER(WostField)), c_int32, c_int32, ctypes.c_char_p,
                                                     c_int64, POINTER(c_int64)]),
+        "wost_tally_cell": (c_int32, [POINTER(WostTallyGrid), POINTER(c_float), c_int64, POINTER(c_int32)]),
+        "wost_tally_quantize": (c_int32, [POINTER(c_float), c_int64, c_int32, c_int64, POINTER(c_int64),
+                                          POINTER(c_uint8)]),
+        "wost_tally_limit": (c_int32, [c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int64)]),
+        "wost_tally_default_scale": (c_int32, [H, c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int32)]),
+        "wost_solve_range_tally": (c_int32, [H, POINTER(c_float), c_int64, c_int64, c_int64, c_int64, c_int32, c_float,
+                                             c_uint64, POINTER(WostTallyGrid), c_int32, c_int32, POINTER(c_double),
+                                             POINTER(c_double), POINTER(c_float), POINTER(c_uint32), POINTER(c_int64),
+                                             POINTER(c_int64)]),
+        "wost_kernel_source_tally": (c_int32, [POINTER(WostProblem), ctypes.c_char_p, c_int64, POINTER(c_int64)]),
         "wost_comm_unique_id": (c_int32, [POINTER(c_uint8)]),
         "wost_comm_create": (c_int32, [POINTER(c_uint8), c_int32, c_int32, c_int32, POINTER(c_void_p)]),
         "wost_comm_destroy": (None, [c_void_p]),

@@ -2436,4 +2436,55 @@ WOST_HD bool point_visible(VP sv, float px, float py, int xcode, float zx, float
     return false;
 }
 
+// ---- Green's function maps (wost_solve_range_tally) ----
+
+// Edge i of a tally grid's axis: the float32 number fl(fl(i * d) + o). Two roundings, no FMA;
+// i is exact as a float (|i| <= WOST_TALLY_MAX_CELLS_1D + 1 < 2^24).
+WOST_HD float tally_edge(int i, float o, float d) {
+#pragma clang fp contract(off)
+    const float s = (float)i * d;
+    return s + o;
+}
+
+// The cell of coordinate v on an axis of n cells [e_i, e_{i+1}), or -1 (outside, NaN).
+// The guess g = floor((v - o) * inv_d), inv_d = fl(1 / d), clamped to [-1, n], is within one
+// cell of the answer on an accepted grid (include/wost.h): with u = 2^-24, t = (v - o) / d the
+// exact coordinate in cells and M = max |edge| / d <= 2^20, the computed (v - o) * inv_d is
+// within 3.01 u |t| of t (three roundings), and edge i lies within u (i + M) cells of i (its
+// two roundings), so for v in cell c: c - e <= t < c + 1 + e with e = u (n + 1 + M), and
+// floor(g) is c - 1, c or c + 1 as long as e + 3.01 u (n + 1) < 1: at n, M <= 2^20 it is
+// below 0.32. Neighbouring edges differ by at least d (1 - 2e) > 0, so the cells are disjoint,
+// and one comparison against e_g and e_{g+1} -- recomputed with tally_edge's two operations,
+// nothing loaded -- settles the cell. A v beyond the clamp moves one further out and is outside.
+WOST_HD int tally_axis_cell(float v, float o, float d, float inv_d, int n) {
+#pragma clang fp contract(off)
+    float g = __builtin_floorf((v - o) * inv_d);
+    if (!(g >= -1.0f)) g = -1.0f;   // (also a NaN: the comparisons below then change nothing)
+    if (g > (float)n) g = (float)n;
+    int i = (int)g;
+    if (v < tally_edge(i, o, d)) i -= 1;
+    else if (v >= tally_edge(i + 1, o, d)) i += 1;
+    return (v == v && i >= 0 && i < n) ? i : -1;
+}
+
+// The bin of a sample in a tally row: iy * nx + ix, or nx * ny (the outside bin).
+WOST_HD int tally_cell(float x, float y, float x0, float y0, float dx, float dy, float inv_dx, float inv_dy, int nx,
+                       int ny) {
+    const int ix = tally_axis_cell(x, x0, dx, inv_dx, nx);
+    const int iy = tally_axis_cell(y, y0, dy, inv_dy, ny);
+    return (ix < 0 || iy < 0) ? nx * ny : iy * nx + ix;
+}
+
+// A deposit in fixed point: q = rne(d * scale), scale = 2^s (the float32 product is exact but
+// for underflow, where it rounds to a |q| <= 1 quantum). False -- and nothing to add -- when
+// !(|q| < limit): too large a deposit, an overflow to infinity, a NaN. limit is a power of
+// two <= 2^62, exact as a float, so the conversion to int64 is exact.
+WOST_HD bool tally_quantize(float d, float scale, float limit, long long* q) {
+#pragma clang fp contract(off)
+    const float qf = __builtin_rintf(d * scale);
+    const bool ok = __builtin_fabsf(qf) < limit;
+    *q = ok ? (long long)qf : 0ll;
+    return ok;
+}
+
 }  // namespace wost

@@ -105,6 +105,7 @@ int convert_field(const wost_field* in, HostField& out, const char* name);
 // f: N_FIELDS fields (absent ones empty); extra: the model fields after them (Program::models)
 void build_program(const HostField* f, double sigma_bar, Program& out, const std::vector<HostField>* extra = nullptr);
 double estimate_sigma_bar(const std::vector<float>& dverts, const std::vector<float>& nverts, const Program& prog);
+double estimate_alpha_min(const std::vector<float>& dverts, const std::vector<float>& nverts, const Program& prog);
 int convert_models(const wost_model* models, int32_t n, std::vector<HostField>* out);
 uint64_t models_checksum(const std::vector<HostField>& f);
 std::vector<float> segment_angles(const std::vector<float>& nverts);
@@ -194,6 +195,10 @@ struct wost_handle {
     wost::DeviceBuffer<float> d_charges;
     wost::DeviceBuffer<int32_t> d_point_code;   // boundary_code of the query points (WalkArgs::point_code)
     wost::DeviceBuffer<int32_t> d_point_list;   // the point list of a solve (WalkArgs::point_list)
+    // Green's function map of a solve (wost_solve_range_tally): the int64 sums
+    // [n_points][replicas][cells + 1] and the flag word (WalkArgs::tally, tally_flag)
+    wost::DeviceBuffer<long long> d_tally;
+    wost::DeviceBuffer<uint32_t> d_tally_flag;
     bool has_source() const { return fields[wost::SLOT_F].present || !charges.empty(); }
     bool delta = false;
     double sigma_bar = 0.0;
@@ -344,11 +349,11 @@ struct KernelChoice {
     double jit_ms = 0.0;           // host time spent compiling
 };
 KernelVariant kernel_variant(const wost_handle* h, const WalkTraits& t, const KernelShape& ks, bool record,
-                             int n_sources, bool point_list = false);
+                             int n_sources, bool point_list = false, bool tally = false);
 int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* ks);
 JitTry jit_kernel_try(wost_handle* h, const KernelVariant& v, JitTicket* ticket);
 int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, int ns, KernelChoice* kc,
-                  bool point_list = false);
+                  bool point_list = false, bool tally = false);
 
 // ---- wost_solve.cpp ----
 constexpr int64_t kMaxBatchWalks = int64_t(1) << 26;   // 64 Mi walks = 512 MiB of per-walk results
@@ -369,6 +374,17 @@ struct SolveRequest {
     const int32_t* point_ids = nullptr;
     int64_t n_ids = 0;
     int64_t rows() const { return point_ids ? n_ids : n_points; }   // point rows of the outputs
+    // wost_solve_range_tally (null: none): the solve's launches add their deposits to the
+    // handle's tally buffer, which the entry point has sized and zeroed and reads afterwards
+    const struct TallyRequest* tally = nullptr;
+};
+// The tally of a solve: the grid (accepted: tally_grid_check), the rows per point, the scale
+// 2^scale_log2 and the power of two a quantised deposit must stay below.
+struct TallyRequest {
+    wost_tally_grid grid{};
+    int32_t replicas = 1;
+    int32_t scale_log2 = 0;
+    int64_t limit = 1;
 };
 
 // Where its results go on the host (each may be null): rows of 2 * channels + 1 doubles per
@@ -389,6 +405,11 @@ struct SolveOutputs {
     double* combined_point_stats = nullptr;
 };
 int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out);
+
+// ---- wost_tally.cpp ----
+int tally_grid_check(const wost_tally_grid* g);
+int64_t tally_row_walks(int64_t w0, int64_t w1, int32_t R, int64_t* rows);
+int tally_limit(int64_t W, int64_t w0, int64_t w1, int32_t R, int32_t max_steps, int64_t* limit);
 
 // ---- wost_point_sources.cpp ----
 void segments_at(const float* nv, int nn, float x, float y, int32_t* s0, int32_t* s1);

@@ -785,10 +785,13 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
     if (dtree) o << "#define WOST_DIRICHLET_TREE 1\n";
     // walk-range batches place their walks through WalkArgs::point_list (KernelVariant::point_list)
     if (v.point_list) o << "#define WOST_POINT_LIST 1\n";
+    // the source samples' deposits go to WalkArgs::tally (KernelVariant::tally)
+    if (v.tally) o << "#define WOST_TALLY 1\n";
     o << "// generated by libwost (wost_jit.cpp): walk kernel, " << traits_name(t);
     if (nm >= 2) o << ", " << nm << " models";
     if (dtree) o << ", dirichlet tree";
     if (v.point_list) o << ", point list";
+    if (v.tally) o << ", tally";
     o << "\n"
       << "#include \"wost_walk.h\"\n\nnamespace {\nstruct GenFields {\n"
       << "    const float* grid;   // tabulated field values (WOST_FK_GRID) in the program buffer\n"

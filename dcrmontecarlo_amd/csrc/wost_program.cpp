@@ -150,6 +150,24 @@ double estimate_sigma_bar(const std::vector<float>& dverts, const std::vector<fl
     return sb;
 }
 
+// The smallest finite positive alpha on the grid estimate_sigma_bar samples (1 without an
+// alpha field or without such a sample): the tally's default scale bounds a deposit with it.
+double estimate_alpha_min(const std::vector<float>& dverts, const std::vector<float>& nverts, const Program& prog) {
+    const DField& fa = prog.hdr()->field[SLOT_ALPHA];
+    if (!fa.present) return 1.0;
+    Box box;
+    grow_box(box, dverts);
+    grow_box(box, nverts);
+    const std::vector<float> gx = torch_linspace(box.x0, box.x1, 50), gy = torch_linspace(box.y0, box.y1, 50);
+    double lo = INFINITY;
+    for (float x : gx)
+        for (float y : gy) {
+            const float a = field_value(fa, prog.terms(), prog.factors(), prog.grid(), x, y);
+            if (std::isfinite(a) && a > 0.0f) lo = std::min(lo, (double)a);
+        }
+    return std::isfinite(lo) ? lo : 1.0;
+}
+
 // ---- conductivity models (wost_set_models, wost_kernel_source_models) ----
 
 // models[0..n) converted with wost_problem's NULL rules (sigma NULL: 0; alpha NULL: the

@@ -471,11 +471,27 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
         HIP_TRY(d_rec.reserve((size_t)(std::min<int64_t>(R.walks_total, batch_limit) * rec_stride * kRecFloats)));
 
     KernelChoice kc;
-    if ((rc = choose_kernel(h, t, out.records != nullptr, n_src, ns, &kc, listed)) != WOST_OK) return rc;
+    if (rq.tally && (listed || out.records || ns != 1 || !h->charges.empty() || !t.src))
+        return fail(WOST_ERR_UNSUPPORTED, "internal: a tally takes one sampled channel, no point list, no recorder");
+    if ((rc = choose_kernel(h, t, out.records != nullptr, n_src, ns, &kc, listed, rq.tally != nullptr)) != WOST_OK)
+        return rc;
     const int block = kc.shape.block;
     WalkArgs a = fill_walk_args(h, rq, t, kc, d_rec);
     if (listed) a.point_list = h->d_point_list;
-    if ((rc = setup_pools(h, t, n_src, kc.blocks_per_cu, &a)) != WOST_OK) return rc;
+    if (rq.tally) {   // (wost_solve_range_tally has sized and zeroed the buffers)
+        const TallyRequest& T = *rq.tally;
+        a.tally = h->d_tally;
+        a.tally_flag = h->d_tally_flag;
+        a.tally_x0 = T.grid.x0; a.tally_y0 = T.grid.y0;
+        a.tally_dx = T.grid.dx; a.tally_dy = T.grid.dy;
+        a.tally_inv_dx = 1.0f / T.grid.dx; a.tally_inv_dy = 1.0f / T.grid.dy;
+        a.tally_nx = T.grid.nx; a.tally_ny = T.grid.ny;
+        a.tally_replicas = T.replicas;
+        a.tally_scale = std::ldexp(1.0f, T.scale_log2);
+        a.tally_limit = (float)T.limit;
+    }
+    // (a tally kernel runs without walk pools: a parked walk holds no tally row)
+    if (!rq.tally && (rc = setup_pools(h, t, n_src, kc.blocks_per_cu, &a)) != WOST_OK) return rc;
     if ((rc = launch_point_alpha_for(h, t, kc.jfn, n_points, &a)) != WOST_OK) return rc;
     if ((rc = setup_point_sources(h, t, rq, &a)) != WOST_OK) return rc;
 

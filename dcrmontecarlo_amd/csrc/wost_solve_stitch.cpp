@@ -273,6 +273,78 @@ int wost_solve_range_points(wost_handle* h, const float* points, int64_t n_point
     return solve_range(h, rq, outputs(block_stats, point_stats, walk_values, walk_steps), walk_begin, walk_end);
 }
 
+int wost_solve_range_tally(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t walk_begin,
+                           int64_t walk_end, int32_t max_steps, float eps, uint64_t seed, const wost_tally_grid* grid,
+                           int32_t replicas, int32_t scale_log2, double* block_stats, double* point_stats,
+                           float* walk_values, uint32_t* walk_steps, int64_t* tally, int64_t* row_walks) {
+    if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
+    if (h->compat != WOST_COMPAT_FIXED)
+        return fail(WOST_ERR_UNSUPPORTED, "a tally needs compat=\"fixed\": the reference's source sample does not estimate "
+                                          "the integral of G f (quirks Q3, Q13)");
+    if (!h->charges.empty())
+        return fail(WOST_ERR_UNSUPPORTED, "a tally rides the source sample: a handle with point sources "
+                                          "(wost_set_point_sources) samples none; clear them first");
+    if (h->n_sources != 1 || h->n_wavenumbers > 0 || h->n_models > 0)
+        return fail(WOST_ERR_UNSUPPORTED, "a tally takes one channel: the handle scores %d sources x %d wavenumbers x %d "
+                                          "models (wost_set_sources / wost_set_wavenumbers / wost_set_models)",
+                    h->n_sources, std::max(h->n_wavenumbers, 1), std::max(h->n_models, 1));
+    if (!h->fields[SLOT_F].present)
+        return fail(WOST_ERR_INVALID_ARG, "a tally rides the source sample: the handle needs a source field (a constant "
+                                          "0 is enough)");
+    if (!h->jit_enabled)
+        return fail(WOST_ERR_UNSUPPORTED, "a tally needs the field-specialised kernel (disabled by wost_set_jit)");
+    if (!tally) return fail(WOST_ERR_INVALID_ARG, "NULL tally");
+    if (int rc = tally_grid_check(grid)) return rc;
+    if (n_points < 0 || W < 1 || W >= (int64_t(1) << 43))
+        return fail(WOST_ERR_INVALID_ARG, "a tally takes 1 <= walks_per_point < 2^43 and n_points >= 0");
+    if (scale_log2 < -100 || scale_log2 > 100) return fail(WOST_ERR_INVALID_ARG, "scale_log2 must be in [-100, 100]");
+    TallyRequest T;
+    T.grid = *grid;
+    T.replicas = replicas;
+    T.scale_log2 = scale_log2;
+    if (int rc = tally_limit(W, walk_begin, walk_end, replicas, max_steps, &T.limit)) return rc;
+    const int64_t bins = (int64_t)grid->nx * grid->ny + 1;
+    if (n_points > 0 && (replicas > WOST_TALLY_MAX_BYTES / 8 / bins || n_points > WOST_TALLY_MAX_BYTES / 8 / bins / replicas))
+        return fail(WOST_ERR_INVALID_ARG, "a tally of %lld points x %d replicas x %lld bins exceeds %lld bytes",
+                    (long long)n_points, (int)replicas, (long long)bins, (long long)WOST_TALLY_MAX_BYTES);
+    const size_t entries = (size_t)(n_points * replicas * bins);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(h->d_tally.reserve(std::max<size_t>(entries, 1)));
+    HIP_TRY(h->d_tally_flag.reserve(1));
+    HIP_TRY(hipMemsetAsync(h->d_tally, 0, sizeof(long long) * entries, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_tally_flag, 0, sizeof(uint32_t), h->stream));
+
+    SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
+    rq.multi = true;
+    rq.tally = &T;
+    if (int rc = solve_range(h, rq, outputs(block_stats, point_stats, walk_values, walk_steps), walk_begin, walk_end))
+        return rc;
+    uint32_t flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, h->d_tally_flag, sizeof(flag), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (flag != 0u) {
+        // flag - 1 is the largest float32 exponent field E of a scaled deposit that did not fit:
+        // |d * 2^s| < 2^(E - 126). One more bit covers the rounding to the quantum.
+        const int l = (int)std::ilogb((double)T.limit), E = (int)flag - 1;
+        const long long rw = (long long)tally_row_walks(walk_begin, walk_end, replicas, nullptr);
+        const int fit = (int)scale_log2 - (E - 126 - l + 1);
+        if (E >= 255 || fit < -100)
+            return fail(WOST_ERR_INVALID_ARG,
+                        "tally: a deposit is infinite, NaN or beyond every quantum (at the quantum 2^%d its scaled value "
+                        "has float32 exponent field %d; %lld walks x %d steps per row leave 2^%d quanta): the walks' "
+                        "weights diverge, no quantum fits", -(int)scale_log2, E, rw, (int)max_steps, l);
+        return fail(WOST_ERR_INVALID_ARG,
+                    "tally: a deposit reached 2^%d quanta of 2^%d, the most that %lld walks x %d steps per row can sum in "
+                    "64 bits; the largest deposit of this solve lies below 2^%d: pass the quantum 2^%d (scale_log2 %d) or "
+                    "a coarser one", l, -(int)scale_log2, rw, (int)max_steps, E - 126 - (int)scale_log2, -fit, fit);
+    }
+    HIP_TRY(hipMemcpyAsync(tally, h->d_tally, sizeof(long long) * entries, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (row_walks)
+        for (int64_t p = 0; p < n_points; ++p) tally_row_walks(walk_begin, walk_end, replicas, row_walks + p * replicas);
+    return WOST_OK;
+}
+
 int wost_solve_range_combined(wost_handle* h, const float* points, int64_t n_points, const int32_t* point_ids,
                               int64_t n_ids, int64_t W, int64_t walk_begin, int64_t walk_end, int32_t max_steps,
                               float eps, uint64_t seed, const double* weights, int32_t n_combinations,

@@ -51,6 +51,8 @@ struct KernelVariant {
                                      // (poly_distance_tree; records and vertices through L1/L2, nothing staged)
     bool point_list = false;         // walk-range batches take their points from WalkArgs::point_list
                                      // (WOST_POINT_LIST; wost_solve_range_points)
+    bool tally = false;              // the source samples' deposits go to WalkArgs::tally
+                                     // (WOST_TALLY; wost_solve_range_tally)
 };
 
 inline bool operator==(const KernelVariant& a, const KernelVariant& b) {
@@ -58,7 +60,8 @@ inline bool operator==(const KernelVariant& a, const KernelVariant& b) {
            a.n_wavenumbers == b.n_wavenumbers && a.n_charges == b.n_charges && a.n_models == b.n_models &&
            a.block == b.block &&
            a.global_polylines == b.global_polylines && a.tree_stage == b.tree_stage && a.exact_trig == b.exact_trig &&
-           a.dirichlet_tree == b.dirichlet_tree && a.point_list == b.point_list;
+           a.dirichlet_tree == b.dirichlet_tree && a.point_list == b.point_list &&
+           a.tally == b.tally;
 }
 
 }  // namespace wost

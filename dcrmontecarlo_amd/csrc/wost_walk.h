@@ -131,6 +131,17 @@ struct WalkArgs {
     // local walk), though no entry point records a list solve (solve_impl refuses). Null
     // otherwise.
     const int32_t* point_list;
+    // Green's function map (wost_solve_range_tally; read only by kernels built with WOST_TALLY):
+    // tally is [n_points][tally_replicas][tally_nx * tally_ny + 1] int64 sums of fixed-point
+    // deposits (the last entry of a row: the outside bin), tally_flag one word that a deposit
+    // beyond tally_limit raises (tally_deposit: to its exponent field + 1, by an atomic max). The grid as tally_cell (wost_device.h) takes it; tally_scale is
+    // 2^s and tally_limit the power of two a quantised deposit must stay below. Null / 0 otherwise.
+    long long* tally;
+    uint32_t* tally_flag;
+    float tally_x0, tally_y0, tally_dx, tally_dy, tally_inv_dx, tally_inv_dy;
+    int32_t tally_nx, tally_ny;
+    int32_t tally_replicas;
+    float tally_scale, tally_limit;
 };
 
 // The Dirichlet polyline's tree as poly_distance_tree reads it (records and vertices through
@@ -925,6 +936,43 @@ __device__ __forceinline__ Hit intersect_polylines_tree_wave(const SegTree& t, f
 #ifndef WOST_DIRICHLET_TREE
 #define WOST_DIRICHLET_TREE 0
 #endif
+// WOST_TALLY 1 (generated kernels of wost_solve_range_tally, KernelVariant::tally; one channel,
+// no point charges, no recorder, no walk pools): the refill finds the walk's row of
+// WalkArgs::tally, and the source sample of every step that is not clipped adds the deposit a
+// source f == 1 would score there to the row's cell of the sample (tally_deposit). The walks,
+// their values and steps are untouched. The other kernels compile none of it.
+#ifndef WOST_TALLY
+#define WOST_TALLY 0
+#endif
+// The first entry of walk wid's tally row, wid a walk of point pid: row (i / WOST_BLOCK_WALKS)
+// mod replicas of the point, i the walk's index in the point (a function of the walk id
+// alone). The buffer holds fewer than 2^27 entries (WOST_TALLY_MAX_BYTES) and i /
+// WOST_BLOCK_WALKS is below 2^31 (walks_per_point < 2^43): 32 bits.
+WOST_HD uint32_t tally_row_base(const WalkArgs& A, uint64_t wid, uint64_t pid) {
+    const uint64_t i = wid - pid * (uint64_t)A.walks_per_point;
+    const uint32_t row = (uint32_t)(i / (uint64_t)WOST_BLOCK_WALKS) % (uint32_t)A.tally_replicas;
+    return ((uint32_t)pid * (uint32_t)A.tally_replicas + row) * (uint32_t)(A.tally_nx * A.tally_ny + 1);
+}
+// One deposit d at the sample (yx, yy): a no-return 64-bit integer add at device scope to the
+// sample's bin of the row that starts at entry `base`, so that the sums do not depend on the
+// order of arrival. A deposit that does not fit (tally_quantize) is not added and sets the
+// flag word (q is 0 then): the host then fails the solve. The word keeps the largest E + 1
+// seen, E the float32 exponent field of the scaled deposit (|d * scale| < 2^(E - 126); 255:
+// infinite or NaN), so that the host can name a quantum under which every deposit fits.
+__device__ __forceinline__ void tally_deposit(const WalkArgs& A, uint32_t base, float yx, float yy, float d) {
+    const int cell = tally_cell(yx, yy, A.tally_x0, A.tally_y0, A.tally_dx, A.tally_dy, A.tally_inv_dx,
+                                A.tally_inv_dy, A.tally_nx, A.tally_ny);
+    long long q;
+    const bool bad = !tally_quantize(d, A.tally_scale, A.tally_limit, &q);
+    if (WOST_ANY(bad)) {
+        if (bad) atomicMax(A.tally_flag, ((__builtin_bit_cast(uint32_t, d * A.tally_scale) >> 23) & 0xffu) + 1u);
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)__hip_atomic_fetch_add(A.tally + ((size_t)base + (size_t)cell), q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    A.tally[(size_t)base + (size_t)cell] += q;
+#endif
+}
 // Walk pools (TREE kernels): see the exchange in walk_body. WOST_TREE_POOL 0 compiles
 // them out; WOST_POOL_MIN_PUSH: fewest mismatched walks a wave parks at once.
 #ifndef WOST_TREE_POOL
@@ -1046,6 +1094,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                   "model channels need delta tracking, no recorder, no point charges, at most WOST_MAX_SOURCES channels");
     static_assert(PC >= 0 && PC <= WOST_MAX_POINT_CHARGES && (PC == 0 || (FIX && SRC && !REC)),
                   "point sources need compat=\"fixed\", a source mode, no recorder, at most WOST_MAX_POINT_CHARGES charges");
+    static_assert(!WOST_TALLY || (SRC && NS == 1 && NK == 1 && NM == 1 && PC == 0 && !REC),
+                  "a tally needs a source mode, one channel, no point charges, no recorder");
     constexpr int NW = NM * NK;   // weights: wc = m * NK + j
     constexpr int NC = NW * NS;   // channels: c = (m * NK + j) * NS + s
     // (a Dirichlet-tree kernel reads the vertices it needs through global loads)
@@ -1098,7 +1148,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
         for (int i = threadIdx.x; i < kGnormCells; i += blockDim.x) sG[i] = g[i];
     }
     // this workgroup's walk pools (header: lock, walks parked near, walks parked far)
-    uint32_t* const pool = (TREE && WOST_TREE_POOL && NK == 1 && PC == 0 && NM == 1 && A.pool != nullptr)
+    // (a parked walk holds no tally row: tally kernels run without pools)
+    uint32_t* const pool = (TREE && WOST_TREE_POOL && !WOST_TALLY && NK == 1 && PC == 0 && NM == 1 && A.pool != nullptr)
                                ? A.pool + (size_t)blockIdx.x * (size_t)A.pool_wg_words : nullptr;
     if (pool != nullptr && threadIdx.x < 4) pool[threadIdx.x] = 0u;
     __syncthreads();
@@ -1157,6 +1208,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     bool onB = false;           // onBoundary
     float phi = 0.f;            // atan2 of currentNormal (:228), set when onB
     int xcode = 0;              // (PC > 0) boundary_code of the current point: its segment and inward side
+#if WOST_TALLY
+    uint32_t trow = 0u;         // first entry of this walk's tally row (tally_row_base)
+#endif
     float ax[NM];               // alpha(current_point), cached (one per model)
 #pragma unroll
     for (int m = 0; m < NM; ++m) ax[m] = 1.f;
@@ -1340,6 +1394,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 WOST_WALK_OF_LOCAL(A, lid, wid, pid)
                 pw = philox_walk(wid, A.key0, A.key1);
                 if (WOST_PHILOX_AHEAD) rn_ahead = philox_draw(pw, 0u, A.key0, A.key1);
+#if WOST_TALLY
+                trow = tally_row_base(A, wid, pid);
+#endif
                 const float2 q = A.points[pid];
                 px = q.x; py = q.y;
                 k = 0; dD = FIX ? WOST_INF : 1.0f; onB = false; phi = 0.f;
@@ -1707,6 +1764,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                         c = (f * gnorm) * f_rsq(aj.v * ax[0]) * w[0];  // :253-254
                     else
                         c = f * ((r * r) / 4.0f);                        // :256, utils.py:61
+#if WOST_TALLY   // what f == 1.0f scores here: (1.0f * gnorm) is gnorm, 1.0f * (r * r / 4) is r * r / 4
+                    tally_deposit(A, trow, yx, yy, DELTA ? (gnorm * f_rsq(aj.v * ax[0])) * w[0] : (r * r) / 4.0f);
+#endif
                 }
                 total[0] = total[0] + c;                                 // :258
                 cv = c;

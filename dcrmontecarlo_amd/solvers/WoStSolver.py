@@ -223,7 +223,8 @@ def _problem(dxy, nxy, g, f, sigma, alpha, compat, device, sigma_bar):
 def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoundary=None, source=None,
                   sigma=None, alpha=None, *, sigma_bar: float | None = None, compat: str = "reference",
                   sources=None, n_wavenumbers: int = 0, models=None, options: dict | None = None,
-                  dirichlet_tree: int | None = None, dirichlet_tree_leaf: int = 0, point_list: bool = False) -> str:
+                  dirichlet_tree: int | None = None, dirichlet_tree_leaf: int = 0, point_list: bool = False,
+                  tally: bool = False) -> str:
     """HIP source of the field-specialised walk kernel a WostSolver_2D with these
     arguments would compile (no device needed; wost_kernel_source). sources: the fields
     of a multi-source solve (solve_sources; wost_kernel_source_sources); n_wavenumbers: the
@@ -236,7 +237,11 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
     single-source kernel only), dirichlet_tree_leaf its leaf_segments; point_list: the kernel
     a solve with a point list launches (solve_range(point_ids=...), solve_to_tolerance;
     wost_kernel_source_point_list; with sources, wavenumbers and models, not with options or
-    dirichlet_tree)."""
+    dirichlet_tree); tally: the kernel solve_greens_map launches (wost_kernel_source_tally;
+    compat="fixed" and a source, and none of the other keywords: a tally takes one channel)."""
+    if tally and (point_list or options or dirichlet_tree is not None or sources or n_wavenumbers or models is not None):
+        raise ValueError("tally: one channel only -- not together with sources, n_wavenumbers, models, point_list, "
+                         "options or dirichlet_tree")
     if point_list and (options or dirichlet_tree is not None):
         raise ValueError("point_list: not together with options or dirichlet_tree")
     if options and (sources or n_wavenumbers or models is not None):
@@ -276,6 +281,8 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
     if dirichlet_tree is not None:
         call = lambda buf, cap: _lib.lib.wost_kernel_source_dirichlet_tree(
             ctypes.byref(prob), int(dirichlet_tree), int(dirichlet_tree_leaf), 0, 0, buf, cap, ctypes.byref(n))
+    if tally:
+        call = lambda buf, cap: _lib.lib.wost_kernel_source_tally(ctypes.byref(prob), buf, cap, ctypes.byref(n))
     _lib.check(call(None, 0), "wost_kernel_source")
     buf = ctypes.create_string_buffer(n.value + 1)
     _lib.check(call(buf, n.value + 1), "wost_kernel_source")
@@ -539,6 +546,100 @@ class WostSolver_2D:
         _lib.check(rc, "WostSolver_2D.solve_range")
         self.last_timing = self.timing()
         return bs
+
+    def solve_greens_map(self, solvePoints, grid, nWalks=1000, maxSteps=1000, eps=1e-4, *, seed: int = 0,
+                         replicas: int = 8, quantum: float | None = None, walk_begin: int = 0,
+                         walk_end: int | None = None, return_history: bool = False, return_walks: bool = False):
+        """A solve that also tallies its walks' source samples on ``grid`` (a
+        :class:`dcrmontecarlo_amd.greens_map.TallyGrid` or its six values x0, y0, dx, dy, nx,
+        ny): a Monte-Carlo map of the Green's function G(x_p, .) of every query point, from
+        the walks an ordinary solve takes (wost_solve_range_tally). The operator
+        is self-adjoint, so row p is also the potential a unit point current at x_p produces
+        everywhere on the grid. Returns a :class:`~dcrmontecarlo_amd.greens_map.GreensMap`.
+
+        compat="fixed" only (NotImplementedError otherwise), one channel (no set_wavenumbers,
+        set_models or set_point_sources in force), field-specialised kernel only. The walks,
+        and ``u`` / ``stats`` of the result, are bit for bit those of solve_range with the
+        solver's own source; a solver without a source gets the constant 0 for the call (the
+        tally rides the source sample). Walk i of a point goes to replica row (i / 4096) mod
+        ``replicas``; the rows give the standard errors. ``quantum`` = 2^-s is the value of one
+        integer unit (rounded down to a power of two; None: chosen from a bound on one
+        deposit); a deposit too large for it raises ValueError naming a quantum that fits.
+        walk_begin / walk_end (block-aligned): a shard of the walks; shards add up
+        (``map_a + map_b``) to the full solve's integers. A query point on the Neumann
+        polyline starts as in every field-source solve.
+        return_walks: also return (values float32 [N, walks], steps uint32 [N, walks])."""
+        from ..greens_map import GreensMap, _c_grid, as_grid
+
+        if return_history:
+            raise NotImplementedError("solve_greens_map records no history: use solve(return_history=True)")
+        if self.compat != "fixed":
+            raise NotImplementedError("solve_greens_map needs compat=\"fixed\": the reference's source sample does not "
+                                      "estimate the integral of G f (quirks Q3, Q13)")
+        for what, on in (("wavenumbers (set_wavenumbers)", self.wavenumbers is not None),
+                         ("models (set_models)", self.models is not None),
+                         ("point sources (set_point_sources)", self.point_sources is not None)):
+            if on:
+                raise NotImplementedError(f"solve_greens_map tallies one channel: the solver has {what} set; clear "
+                                          "them first")
+        if self.num_channels() != 1:   # (sources_installed: installing the zero source below would drop them)
+            raise NotImplementedError(f"solve_greens_map tallies one channel: the handle scores {self.num_channels()} "
+                                      "(extra sources are installed)")
+        p = _points_np(solvePoints)
+        n = p.shape[0]
+        nWalks = _walk_count(nWalks)
+        w0, w1 = int(walk_begin), nWalks if walk_end is None else int(walk_end)
+        R = int(replicas)
+        g = as_grid(grid)
+        cg = _c_grid(g)
+        if R < 1:
+            raise ValueError(f"replicas must be >= 1 (got {replicas})")
+        if g.nx < 1 or g.ny < 1:
+            raise ValueError("the grid needs nx, ny >= 1")
+        bins = g.nx * g.ny + 1
+        if n * R * bins * 8 > _lib.WOST_TALLY_MAX_BYTES:
+            raise ValueError(f"a tally of {n} points x {R} replicas x {bins} bins exceeds "
+                             f"{_lib.WOST_TALLY_MAX_BYTES} bytes: fewer points per call, replicas or cells")
+        own = self.source
+
+        @contextlib.contextmanager
+        def zero_source():   # the tally rides the source sample: a constant 0 for the call
+            wf, keep = _lib.make_field(const(0.0))
+            _lib.check(_lib.lib.wost_set_field(self._h, _lib.SLOT_SOURCE, ctypes.pointer(wf)), "solve_greens_map")
+            try:
+                yield
+            finally:
+                _lib.check(_lib.lib.wost_set_field(self._h, _lib.SLOT_SOURCE, None), "solve_greens_map")
+
+        with (zero_source() if own is None else contextlib.nullcontext()):
+            if quantum is None:
+                s = ctypes.c_int32(0)
+                _lib.check(_lib.lib.wost_tally_default_scale(self._h, nWalks, w0, w1, R, int(maxSteps), ctypes.byref(s)),
+                           "solve_greens_map")
+                s = int(s.value)
+            else:
+                if not (quantum > 0 and np.isfinite(quantum)):
+                    raise ValueError(f"quantum must be positive and finite (got {quantum})")
+                s = -int(np.floor(np.log2(float(quantum))))
+            tally = np.zeros((n, R, bins), np.int64)
+            rows = np.zeros((n, R), np.int64)
+            sums = np.zeros((n, 3), np.float64)
+            nw = max(w1 - w0, 0)
+            wv = np.empty((n, nw), np.float32) if return_walks else None
+            ws = np.empty((n, nw), np.uint32) if return_walks else None
+            i64 = ctypes.POINTER(ctypes.c_int64)
+            _lib.check(_lib.lib.wost_solve_range_tally(
+                self._h, _lib.fptr(p), n, nWalks, w0, w1, int(maxSteps), float(eps), _lib.seed64(seed), ctypes.byref(cg),
+                R, s, None, _lib.dptr(sums), _lib.fptr(wv), _lib.u32ptr(ws), tally.ctypes.data_as(i64),
+                rows.ctypes.data_as(i64)), "WostSolver_2D.solve_greens_map")
+        self.last_timing = self.timing()
+        self.last_point_sums = sums
+        u = (sums[:, 0] / max(nw, 1)).astype(np.float32).reshape(n, 1)
+        t = self.last_timing
+        st = stats_from_sums(sums, max(nw, 1), t["total_steps"], t["walk_kernel_ms"], t["total_ms"])
+        gm = GreensMap(tally[:, :, :-1].reshape(n, R, g.ny, g.nx).copy(), tally[:, :, -1].copy(), rows, 2.0 ** -s, g,
+                       _like(u, solvePoints), st)
+        return (gm, wv, ws) if return_walks else gm
 
     def _combination_weights(self, weights) -> np.ndarray:
         """``weights`` as contiguous float64 [L, C] for the C installed channels (ValueError

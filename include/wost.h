@@ -450,6 +450,79 @@ int wost_solve_range_points(wost_handle* h, const float* points, int64_t n_point
                             double* block_stats, double* point_stats,
                             float* walk_values, uint32_t* walk_steps);
 
+/* Green's function maps (no reference counterpart): a wost_solve_range that
+ * also tallies every walk's source samples on a grid. compat="fixed" handles only.
+ *
+ * The grid: nx x ny cells. The x edges are the float32 numbers e_i = fl(fl(i * dx) + x0), i =
+ * 0..nx (two roundings, no FMA), cell i is the half-open interval [e_i, e_{i+1}); likewise in
+ * y. A sample outside every cell, or a NaN, belongs to the one extra "outside" bin. Accepted
+ * grids: 1 <= nx, ny <= WOST_TALLY_MAX_CELLS_1D, finite origin, 2^-60 <= dx, dy <= 2^60, and
+ * every edge within WOST_TALLY_MAX_CELLS_1D cell widths of 0 (|x0|, |x0 + nx dx| <= 2^20 dx):
+ * then the float32 guess floor((x - x0) * fl(1 / dx)) is provably within one cell of the
+ * sample's cell, and one comparison against the recomputed edges settles it. */
+typedef struct wost_tally_grid {
+    float x0, y0;    /* the lower left corner */
+    float dx, dy;    /* cell widths */
+    int32_t nx, ny;
+} wost_tally_grid;
+#define WOST_TALLY_MAX_CELLS_1D (1 << 20)
+/* the tally buffer [n_points][replicas][nx * ny + 1] of int64 may hold at most this many bytes */
+#define WOST_TALLY_MAX_BYTES ((int64_t)1 << 30)
+
+/* The cell of each point (points[2i], points[2i+1]) as the kernels find it, on the host:
+ * out[i] = iy * nx + ix, or nx * ny for the outside bin. WOST_ERR_INVALID_ARG for a grid that
+ * is not accepted (above). */
+int wost_tally_cell(const wost_tally_grid* grid, const float* points, int64_t n, int32_t* out);
+/* The kernels' fixed-point conversion of deposits, on the host: out[i] = round-to-nearest-even
+ * (d[i] * 2^scale_log2) (the product formed in float32; exact but for underflow) and ok[i] = 1
+ * when |out[i]| < limit, else ok[i] = 0 and out[i] = 0 (a NaN, an overflow). scale_log2 in
+ * [-100, 100]; limit a power of two in [1, 2^62]. */
+int wost_tally_quantize(const float* d, int64_t n, int32_t scale_log2, int64_t limit, int64_t* out, uint8_t* ok);
+/* The largest deposit magnitude a tally solve accepts (exclusive): the largest power of two L
+ * with max_row_walks * max_steps * L < 2^63, where max_row_walks is the most walks of
+ * [walk_begin, walk_end) that one replica row of a point receives. */
+int wost_tally_limit(int64_t walks_per_point, int64_t walk_begin, int64_t walk_end, int32_t replicas,
+                     int32_t max_steps, int64_t* limit);
+/* The scale a tally solve uses by default (the facade's quantum = 2^-scale_log2): the largest
+ * one at which 2^16 times a cheap bound B on one deposit stays below wost_tally_limit. B is
+ * diag^2 / 4 of the Dirichlet polyline's bounding box without delta tracking (a deposit is
+ * r^2 / 4) and 1 / (sigma_bar * min alpha) with it, alpha sampled on the 50 x 50 grid that
+ * the sigma_bar estimate samples. B is an estimate -- it leaves out the walk's weight, which
+ * a sigma_bar below sigma' lets grow without bound; the solve's check is the guarantee. */
+int wost_tally_default_scale(const wost_handle* h, int64_t walks_per_point, int64_t walk_begin, int64_t walk_end,
+                             int32_t replicas, int32_t max_steps, int32_t* scale_log2);
+
+/* wost_solve_range (same arguments, same outputs, bit for bit the same walks, values, steps,
+ * block and point rows) that also tallies: every live walk, at every step whose source sample
+ * y is not clipped, adds the deposit
+ *      delta tracking:     d = (G_norm * rsq(alpha(y) alpha(x))) * w
+ *      no delta tracking:  d = (r * r) / 4
+ * -- the value a source f == 1 scores at that step -- as q = rne(d * 2^scale_log2) to the
+ * int64 cell of y in row (i / WOST_BLOCK_WALKS) mod replicas of its point, i the walk's index
+ * in [0, walks_per_point). Integer sums: the result does not depend on the launch shape or
+ * the order of arrival, and two walk-range shards merge by integer addition.
+ *   tally     [n_points][replicas][nx * ny + 1] int64 (the last entry: the outside bin)
+ *   row_walks [n_points][replicas] int64: the walks of the range that went to each row
+ * A deposit with !(|q| < wost_tally_limit) is not added; the solve then fails with
+ * WOST_ERR_INVALID_ARG, names a scale that would fit, and returns no tally.
+ *   WOST_ERR_UNSUPPORTED  a compat="reference" handle (its source sample does not estimate
+ *                         the integral of G f: quirks Q3, Q13); extra sources, wavenumbers,
+ *                         models or point charges on the handle; the field-specialised
+ *                         kernel disabled (wost_set_jit) or not buildable
+ *   WOST_ERR_INVALID_ARG  no source field on the handle; a grid that is not accepted;
+ *                         replicas < 1; scale_log2 outside [-100, 100]; a tally buffer above
+ *                         WOST_TALLY_MAX_BYTES; walks_per_point >= 2^43; NULL tally
+ * The field-specialised kernel of a tally solve is one of its own (WOST_TALLY); the solve
+ * waits for its compile and never starts on the precompiled kernel. Segment-tree launches
+ * run without walk pools. */
+int wost_solve_range_tally(wost_handle* h, const float* points, int64_t n_points,
+                           int64_t walks_per_point, int64_t walk_begin, int64_t walk_end,
+                           int32_t max_steps, float eps, uint64_t seed,
+                           const wost_tally_grid* grid, int32_t replicas, int32_t scale_log2,
+                           double* block_stats, double* point_stats,
+                           float* walk_values, uint32_t* walk_steps,
+                           int64_t* tally, int64_t* row_walks);
+
 /* Weighted channel combinations, reduced on the device (no reference counterpart; DESIGN.md
  * 7e). The C = wost_num_channels(h) channels of a launch share their walks and are
  * correlated, so the standard error of a linear combination sum_c w_c u_c (a 2.5-D
@@ -722,6 +795,12 @@ int wost_kernel_source_models(const wost_problem* problem, const wost_model* mod
 int wost_kernel_source_point_list(const wost_problem* problem, const wost_model* models, int32_t n_models,
                                   const wost_field* const* sources, int32_t n_sources, int32_t n_wavenumbers,
                                   char* out, int64_t capacity, int64_t* length);
+
+/* wost_kernel_source's kernel as wost_solve_range_tally launches it (WOST_TALLY): the refill
+ * finds the walk's tally row and the source sample's deposit is added to its cell. Nothing
+ * else of the source differs. With the solve's refusals that need no device
+ * (compat="reference": WOST_ERR_UNSUPPORTED; no source field: WOST_ERR_INVALID_ARG). Host only. */
+int wost_kernel_source_tally(const wost_problem* problem, char* out, int64_t capacity, int64_t* length);
 
 /* The same for a handle with n_charges point charges in n_sources source channels
  * (wost_set_point_sources; the problem must have no source field) and n_wavenumbers

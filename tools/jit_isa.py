@@ -7,7 +7,9 @@ kernel's resource usage and an instruction histogram (static counts).
 Usage: python tools/jit_isa.py dcr_dipole [--out build/jit] [--show] [--votes] [--wavenumbers NK] [--sources NS]
        [--point-charges PC]   (point sources: PC charges in NS sources, compat="fixed")
        [--models M]           (set_models: the scenario's fields, a constant background, then perturbed copies)
-       [--point-list]         (the kernel of solve_range(point_ids=...) / solve_to_tolerance: WOST_POINT_LIST)"""
+       [--point-list]         (the kernel of solve_range(point_ids=...) / solve_to_tolerance: WOST_POINT_LIST)
+       [--tally]              (the kernel of solve_greens_map: WOST_TALLY; compat="fixed", the scenario's own source)
+       [--compat fixed]       (the plain kernel under compat="fixed": what --tally is compared with)"""
 import argparse
 import collections
 import os
@@ -98,9 +100,14 @@ def main():
                          "constant-alpha background, then copies with a scaled conductivity")
     ap.add_argument("--point-list", action="store_true",
                     help="the point-list kernel (solve_range(point_ids=...), solve_to_tolerance); not with --point-charges")
+    ap.add_argument("--tally", action="store_true",
+                    help="the tally kernel (solve_greens_map; compat=\"fixed\"); not with the channel options")
+    ap.add_argument("--compat", default="reference", choices=("reference", "fixed"), help="the kernel's estimators")
     a = ap.parse_args()
     if a.point_list and a.point_charges:
         ap.error("--point-list: not together with --point-charges")
+    if a.tally and (a.point_list or a.point_charges or a.sources or a.wavenumbers or a.models):
+        ap.error("--tally: one channel only")
     if a.waves:
         os.environ["WOST_JIT_WAVES"] = a.waves
     from dcrmontecarlo_amd import scenarios as S
@@ -117,16 +124,18 @@ def main():
         models += [(sc.sigma, S.dcr_alpha_geophysical(1.0 + 0.01 * k) if dcr else sc.alpha * (1.0 + 0.01 * k))
                    for k in range(1, a.models - 1)]
         models = models[:a.models]
-    if a.point_charges:
+    if a.tally:
+        src = sc.kernel_source(compat="fixed", tally=True)
+    elif a.point_charges:
         src = sc.kernel_source_points(a.point_charges, max(a.sources, 1), n_wavenumbers=a.wavenumbers)
     else:
         src = sc.kernel_source(n_wavenumbers=a.wavenumbers, **({"sources": [sc.f * (1.0 + k) for k in range(a.sources)]}
                                                                if a.sources else {}),
-                               **({"models": models} if models else {}), point_list=a.point_list)
+                               **({"models": models} if models else {}), point_list=a.point_list, compat=a.compat)
     os.makedirs(a.out, exist_ok=True)
     tag = a.scenario + (f"_nk{a.wavenumbers}" if a.wavenumbers else "") + (f"_ns{a.sources}" if a.sources else "") + (
         f"_pc{a.point_charges}" if a.point_charges else "") + (f"_nm{a.models}" if a.models else "") + (
-        "_list" if a.point_list else "")
+        "_list" if a.point_list else "") + ("_tally" if a.tally else "_fixed" if a.compat == "fixed" else "")
     hip = os.path.join(a.out, f"{tag}.hip")
     with open(hip, "w") as f:
         f.write(src)
