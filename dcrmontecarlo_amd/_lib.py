@@ -32,6 +32,7 @@ WOST_DTREE_MIN_SEGMENTS_DEFAULT = 128   # include/wost.h (wost_set_dirichlet_tre
 WOST_DTREE_LEAF_DEFAULT = 10
 WOST_TALLY_MAX_CELLS_1D = 1 << 20   # include/wost.h (wost_tally_grid)
 WOST_TALLY_MAX_BYTES = 1 << 30      # include/wost.h (wost_solve_range_tally)
+WOST_TALLY_MAX_MAPS = 4             # include/wost.h (wost_solve_range_tally_channels)
 WOST_TRIG = {"auto": 0, "exact": 1, "fast": 2}   # include/wost.h wost_trig
 WOST_SAMPLER_TABLE_N = 4097
 COMPAT = {"reference": 0, "fixed": 1}
@@ -180,6 +181,18 @@ def _load():
                                              POINTER(c_double), POINTER(c_float), POINTER(c_uint32), POINTER(c_int64),
                                              POINTER(c_int64)]),
         "wost_kernel_source_tally": (c_int32, [POINTER(WostProblem), ctypes.c_char_p, c_int64, POINTER(c_int64)]),
+        "wost_tally_check_weights": (c_int32, [POINTER(c_float), c_int32, c_int32]),
+        "wost_tally_weighted": (c_int32, [POINTER(c_float), c_int64, c_int32, POINTER(c_float), c_int32,
+                                          POINTER(c_float)]),
+        "wost_tally_map_row": (c_int32, [c_int64, c_int32, c_int32, c_int64, c_int64, c_int64, c_int32,
+                                         POINTER(c_int64)]),
+        "wost_solve_range_tally_channels": (c_int32, [H, POINTER(c_float), c_int64, c_int64, c_int64, c_int64, c_int32,
+                                                      c_float, c_uint64, POINTER(WostTallyGrid), c_int32, c_int32,
+                                                      POINTER(c_float), c_int32, POINTER(c_double), POINTER(c_double),
+                                                      POINTER(c_float), POINTER(c_uint32), POINTER(c_int64),
+                                                      POINTER(c_int64)]),
+        "wost_kernel_source_tally_channels": (c_int32, [POINTER(WostProblem), POINTER(WostModel), c_int32, c_int32,
+                                                        c_int32, ctypes.c_char_p, c_int64, POINTER(c_int64)]),
         "wost_comm_unique_id": (c_int32, [POINTER(c_uint8)]),
         "wost_comm_create": (c_int32, [POINTER(c_uint8), c_int32, c_int32, c_int32, POINTER(c_void_p)]),
         "wost_comm_destroy": (None, [c_void_p]),

@@ -2487,4 +2487,37 @@ WOST_HD bool tally_quantize(float d, float scale, float limit, long long* q) {
     return ok;
 }
 
+// ---- channel maps (wost_solve_range_tally_channels; DESIGN.md 7f "Channel maps") ----
+
+// One map's deposit from the n channels' deposits d: the weighted sum in float32, channels
+// ascending, each product and each sum rounded on its own (no FMA; wost_combine.h does the
+// same in double). A zero weight skips its channel, whatever it holds: a unit row returns
+// d[c] itself -- 0.0f + 1.0f * d[c] is d[c] (but for the sign of a zero, which quantises to
+// the same 0) -- with infinities or NaNs in the other channels. WP: a pointer to the row's n
+// weights (the kernels read them through the constant address space: scalar loads).
+template <class WP>
+WOST_HD float tally_weighted(WP tw, const float* d, int n) {
+#pragma clang fp contract(off)
+    float v = 0.0f;
+#pragma unroll
+    for (int c = 0; c < n; ++c) {
+        const float wc = tw[c];
+        if (wc != 0.0f) {
+            const float p = wc * d[c];
+            v = v + p;
+        }
+    }
+    return v;
+}
+
+// The first entry of the n_maps sub-rows of a walk in the tally buffer
+// [n_points][replicas][n_maps][bins]: walk i of point pid (its index in the point) goes to
+// row (i / WOST_BLOCK_WALKS) mod replicas; map t's sub-row starts bins * t further on. The
+// buffer holds fewer than 2^27 entries (WOST_TALLY_MAX_BYTES covers the factor n_maps) and
+// i / WOST_BLOCK_WALKS is below 2^31 (walks_per_point < 2^43): 32 bits.
+WOST_HD uint32_t tally_maps_row(uint64_t i, uint32_t pid, uint32_t replicas, uint32_t n_maps, uint32_t bins) {
+    const uint32_t row = (uint32_t)(i / (uint64_t)WOST_BLOCK_WALKS) % replicas;
+    return ((pid * replicas + row) * n_maps) * bins;
+}
+
 }  // namespace wost

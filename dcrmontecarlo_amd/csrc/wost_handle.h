@@ -199,6 +199,9 @@ struct wost_handle {
     // [n_points][replicas][cells + 1] and the flag word (WalkArgs::tally, tally_flag)
     wost::DeviceBuffer<long long> d_tally;
     wost::DeviceBuffer<uint32_t> d_tally_flag;
+    // ... and of a channel-map solve (wost_solve_range_tally_channels) the combination weights
+    // float [n_maps][channels] (WalkArgs::tally_weights), uploaded per solve
+    wost::DeviceBuffer<float> d_tally_weights;
     bool has_source() const { return fields[wost::SLOT_F].present || !charges.empty(); }
     bool delta = false;
     double sigma_bar = 0.0;
@@ -349,11 +352,11 @@ struct KernelChoice {
     double jit_ms = 0.0;           // host time spent compiling
 };
 KernelVariant kernel_variant(const wost_handle* h, const WalkTraits& t, const KernelShape& ks, bool record,
-                             int n_sources, bool point_list = false, bool tally = false);
+                             int n_sources, bool point_list = false, bool tally = false, int tally_maps = 0);
 int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* ks);
 JitTry jit_kernel_try(wost_handle* h, const KernelVariant& v, JitTicket* ticket);
 int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, int ns, KernelChoice* kc,
-                  bool point_list = false, bool tally = false);
+                  bool point_list = false, bool tally = false, int tally_maps = 0);
 
 // ---- wost_solve.cpp ----
 constexpr int64_t kMaxBatchWalks = int64_t(1) << 26;   // 64 Mi walks = 512 MiB of per-walk results
@@ -385,6 +388,10 @@ struct TallyRequest {
     int32_t replicas = 1;
     int32_t scale_log2 = 0;
     int64_t limit = 1;
+    // channel maps (wost_solve_range_tally_channels; 0: the one-channel tally): the maps kept and
+    // their weights [n_maps][channels] on the host (checked: tally_check_weights)
+    int32_t n_maps = 0;
+    const float* weights = nullptr;
 };
 
 // Where its results go on the host (each may be null): rows of 2 * channels + 1 doubles per
@@ -410,6 +417,7 @@ int solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs& out);
 int tally_grid_check(const wost_tally_grid* g);
 int64_t tally_row_walks(int64_t w0, int64_t w1, int32_t R, int64_t* rows);
 int tally_limit(int64_t W, int64_t w0, int64_t w1, int32_t R, int32_t max_steps, int64_t* limit);
+int tally_check_weights(const float* weights, int32_t n_maps, int32_t n_channels);
 
 // ---- wost_point_sources.cpp ----
 void segments_at(const float* nv, int nn, float x, float y, int32_t* s0, int32_t* s1);

@@ -787,11 +787,14 @@ std::string jit_generate(const Options& opt, const KernelVariant& v, const Progr
     if (v.point_list) o << "#define WOST_POINT_LIST 1\n";
     // the source samples' deposits go to WalkArgs::tally (KernelVariant::tally)
     if (v.tally) o << "#define WOST_TALLY 1\n";
+    // ... or, per map, the weighted combination of the channels' (KernelVariant::tally_maps)
+    if (v.tally_maps > 0) o << "#define WOST_TALLY_MAPS " << v.tally_maps << "\n";
     o << "// generated by libwost (wost_jit.cpp): walk kernel, " << traits_name(t);
     if (nm >= 2) o << ", " << nm << " models";
     if (dtree) o << ", dirichlet tree";
     if (v.point_list) o << ", point list";
     if (v.tally) o << ", tally";
+    if (v.tally_maps > 0) o << ", " << v.tally_maps << (v.tally_maps == 1 ? " tally map" : " tally maps");
     o << "\n"
       << "#include \"wost_walk.h\"\n\nnamespace {\nstruct GenFields {\n"
       << "    const float* grid;   // tabulated field values (WOST_FK_GRID) in the program buffer\n"

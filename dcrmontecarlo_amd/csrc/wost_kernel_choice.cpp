@@ -130,13 +130,13 @@ JitTry jit_kernel_try(wost_handle* h, const KernelVariant& v, JitTicket* ticket)
 // The field-specialised kernel of that shape for walks with traits `t` that score n_sources
 // sources: the one place that reads the rest of the variant off the handle.
 KernelVariant kernel_variant(const wost_handle* h, const WalkTraits& t, const KernelShape& ks, bool record,
-                             int n_sources, bool point_list, bool tally) {
+                             int n_sources, bool point_list, bool tally, int tally_maps) {
     return KernelVariant{.traits = t, .record = record, .n_sources = n_sources,
                          .n_wavenumbers = t.delta ? h->n_wavenumbers : 0,   // (0: the kernel without the k2 read)
                          .n_charges = (int)h->charges.size(), .n_models = t.delta ? h->n_models : 0,
                          .block = ks.block, .global_polylines = ks.gpoly,
                          .tree_stage = ks.stage(), .exact_trig = exact_trig_of(h), .dirichlet_tree = ks.dtree,
-                         .point_list = point_list, .tally = tally};
+                         .point_list = point_list, .tally = tally, .tally_maps = tally_maps};
 }
 
 int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* ks) {
@@ -176,7 +176,7 @@ int first_kernel_shape(const wost_handle* h, const WalkTraits& t, KernelShape* k
 // first_kernel_shape, staging less of the segment tree while what it stages costs the CU
 // its waves; the precompiled one when that is disabled or could not be built.
 int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, int ns, KernelChoice* kc,
-                  bool point_list, bool tally) {
+                  bool point_list, bool tally, int tally_maps) {
     *kc = KernelChoice{};
     KernelShape& ks = kc->shape;
     int rc;
@@ -184,9 +184,9 @@ int choose_kernel(wost_handle* h, const WalkTraits& t, bool record, int n_src, i
     int lds_cap = -1;
     // looks ks up and measures its occupancy
     auto lookup = [&]() -> int {
-        kc->jfn = jit_kernel(h, kernel_variant(h, t, ks, record, n_src, point_list, tally), &kc->jit_ms);
+        kc->jfn = jit_kernel(h, kernel_variant(h, t, ks, record, n_src, point_list, tally, tally_maps), &kc->jit_ms);
         if (!kc->jfn) {   // the precompiled kernels run 256-thread workgroups, no staged tree, one channel
-            if (tally)   // (... and tally nothing)
+            if (tally || tally_maps > 0)   // (... and tally nothing)
                 return fail(WOST_ERR_UNSUPPORTED, "a tally needs the field-specialised kernel%s%s",
                             h->jit_enabled ? ": " : " (disabled by wost_set_jit)", h->jit_error.c_str());
             if (point_list)   // (... and read no point list)
@@ -238,7 +238,7 @@ int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources,
                        int32_t n_wavenumbers, int32_t n_charges, char* out, int64_t capacity, int64_t* length,
                        const wost_model* models = nullptr, int32_t n_models = 0, const char* const* opt_names = nullptr,
                        const double* opt_values = nullptr, int32_t n_options = 0, const int32_t* dtree = nullptr,
-                       bool point_list = false, bool tally = false) {
+                       bool point_list = false, bool tally = false, int tally_maps = 0) {
     if (!pb || !length) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
     if (n_options < 0 || (n_options > 0 && (!opt_names || !opt_values)))
         return fail(WOST_ERR_INVALID_ARG, "need n_options >= 0 names and values");
@@ -287,13 +287,15 @@ int kernel_source_impl(const wost_problem* pb, const wost_field* const* sources,
     // the first solve's kernel without a device: 256 threads, nothing of the tree staged
     KernelShape ks0;
     ks0.dtree = use_dtree(h);
-    if (tally) {   // wost_solve_range_tally's refusals that need no device
+    if (tally_maps != 0 && (tally_maps < 1 || tally_maps > WOST_TALLY_MAX_MAPS))
+        return fail(WOST_ERR_INVALID_ARG, "channel maps: n_maps = %d, need 1..%d", (int)tally_maps, WOST_TALLY_MAX_MAPS);
+    if (tally || tally_maps > 0) {   // wost_solve_range_tally's (_channels') refusals that need no device
         if (h->compat != WOST_COMPAT_FIXED)
             return fail(WOST_ERR_UNSUPPORTED, "a tally needs compat=\"fixed\": the reference's source sample does not "
                                               "estimate the integral of G f (quirks Q3, Q13)");
         if (!h->fields[SLOT_F].present) return fail(WOST_ERR_INVALID_ARG, "a tally needs a source field on the handle");
     }
-    KernelVariant v = kernel_variant(h, t, ks0, false, ns, point_list, tally);
+    KernelVariant v = kernel_variant(h, t, ks0, false, ns, point_list, tally, tally_maps);
     // study builds: offline study of the tree kernels' LDS staging (tools/jit_isa.py --stage):
     // the source of staging level WOST_KERNEL_SOURCE_STAGE (2: records and vertices, 1:
     // records, with the tree_lds_block workgroup) instead
@@ -343,6 +345,15 @@ int wost_kernel_source_point_list(const wost_problem* pb, const wost_model* mode
 int wost_kernel_source_tally(const wost_problem* pb, char* out, int64_t capacity, int64_t* length) {
     return kernel_source_impl(pb, nullptr, 0, 0, 0, out, capacity, length, nullptr, 0, nullptr, nullptr, 0, nullptr, false,
                               true);
+}
+
+int wost_kernel_source_tally_channels(const wost_problem* pb, const wost_model* models, int32_t n_models,
+                                      int32_t n_wavenumbers, int32_t n_maps, char* out, int64_t capacity,
+                                      int64_t* length) {
+    if (n_maps < 1 || n_maps > WOST_TALLY_MAX_MAPS)
+        return fail(WOST_ERR_INVALID_ARG, "channel maps: n_maps = %d, need 1..%d", (int)n_maps, WOST_TALLY_MAX_MAPS);
+    return kernel_source_impl(pb, nullptr, 0, n_wavenumbers, 0, out, capacity, length, models, n_models, nullptr, nullptr,
+                              0, nullptr, false, false, n_maps);
 }
 
 int wost_kernel_source_options(const wost_problem* pb, const char* const* names, const double* values,

@@ -151,20 +151,25 @@ double estimate_sigma_bar(const std::vector<float>& dverts, const std::vector<fl
 }
 
 // The smallest finite positive alpha on the grid estimate_sigma_bar samples (1 without an
-// alpha field or without such a sample): the tally's default scale bounds a deposit with it.
+// alpha field or without such a sample), over the handle's alpha and those of the models
+// after it (Program::models): the tally's default scale bounds a deposit with it.
 double estimate_alpha_min(const std::vector<float>& dverts, const std::vector<float>& nverts, const Program& prog) {
-    const DField& fa = prog.hdr()->field[SLOT_ALPHA];
-    if (!fa.present) return 1.0;
+    std::vector<const DField*> alphas;
+    if (prog.hdr()->field[SLOT_ALPHA].present) alphas.push_back(&prog.hdr()->field[SLOT_ALPHA]);
+    for (size_t s = 1; s < prog.models.size(); s += 2)   // (sigma, alpha) pairs of models 1..
+        if (prog.models[s].present) alphas.push_back(&prog.models[s]);
+    if (alphas.empty()) return 1.0;
     Box box;
     grow_box(box, dverts);
     grow_box(box, nverts);
     const std::vector<float> gx = torch_linspace(box.x0, box.x1, 50), gy = torch_linspace(box.y0, box.y1, 50);
     double lo = INFINITY;
     for (float x : gx)
-        for (float y : gy) {
-            const float a = field_value(fa, prog.terms(), prog.factors(), prog.grid(), x, y);
-            if (std::isfinite(a) && a > 0.0f) lo = std::min(lo, (double)a);
-        }
+        for (float y : gy)
+            for (const DField* fa : alphas) {
+                const float a = field_value(*fa, prog.terms(), prog.factors(), prog.grid(), x, y);
+                if (std::isfinite(a) && a > 0.0f) lo = std::min(lo, (double)a);
+            }
     return std::isfinite(lo) ? lo : 1.0;
 }
 

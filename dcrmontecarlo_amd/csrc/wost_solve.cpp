@@ -471,9 +471,12 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
         HIP_TRY(d_rec.reserve((size_t)(std::min<int64_t>(R.walks_total, batch_limit) * rec_stride * kRecFloats)));
 
     KernelChoice kc;
-    if (rq.tally && (listed || out.records || ns != 1 || !h->charges.empty() || !t.src))
-        return fail(WOST_ERR_UNSUPPORTED, "internal: a tally takes one sampled channel, no point list, no recorder");
-    if ((rc = choose_kernel(h, t, out.records != nullptr, n_src, ns, &kc, listed, rq.tally != nullptr)) != WOST_OK)
+    const int tally_maps = rq.tally ? rq.tally->n_maps : 0;   // (0: none, or the one-channel tally)
+    if (rq.tally && (listed || out.records || (tally_maps > 0 ? n_src : ns) != 1 || !h->charges.empty() || !t.src))
+        return fail(WOST_ERR_UNSUPPORTED, "internal: a tally takes one sampled channel (channel maps: one source), no "
+                                          "point list, no recorder");
+    if ((rc = choose_kernel(h, t, out.records != nullptr, n_src, ns, &kc, listed, rq.tally && tally_maps == 0,
+                            tally_maps)) != WOST_OK)
         return rc;
     const int block = kc.shape.block;
     WalkArgs a = fill_walk_args(h, rq, t, kc, d_rec);
@@ -489,6 +492,10 @@ int wost::solve_impl(wost_handle* h, const SolveRequest& rq, const SolveOutputs&
         a.tally_replicas = T.replicas;
         a.tally_scale = std::ldexp(1.0f, T.scale_log2);
         a.tally_limit = (float)T.limit;
+        if (tally_maps > 0) {   // (... and uploaded the weights)
+            a.tally_weights = h->d_tally_weights;
+            a.tally_n_weights = tally_maps * ns;
+        }
     }
     // (a tally kernel runs without walk pools: a parked walk holds no tally row)
     if (!rq.tally && (rc = setup_pools(h, t, n_src, kc.blocks_per_cu, &a)) != WOST_OK) return rc;

@@ -273,10 +273,17 @@ int wost_solve_range_points(wost_handle* h, const float* points, int64_t n_point
     return solve_range(h, rq, outputs(block_stats, point_stats, walk_values, walk_steps), walk_begin, walk_end);
 }
 
-int wost_solve_range_tally(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t walk_begin,
-                           int64_t walk_end, int32_t max_steps, float eps, uint64_t seed, const wost_tally_grid* grid,
-                           int32_t replicas, int32_t scale_log2, double* block_stats, double* point_stats,
-                           float* walk_values, uint32_t* walk_steps, int64_t* tally, int64_t* row_walks) {
+}  // extern "C"
+
+namespace {
+
+// wost_solve_range_tally (n_maps 0, weights null) and wost_solve_range_tally_channels (n_maps
+// maps of the handle's channels): the refusals, the buffers, the solve, the flag, the copy.
+int solve_tally(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t walk_begin,
+                int64_t walk_end, int32_t max_steps, float eps, uint64_t seed, const wost_tally_grid* grid,
+                int32_t replicas, int32_t scale_log2, const float* weights, int32_t n_maps, bool channels,
+                double* block_stats, double* point_stats, float* walk_values, uint32_t* walk_steps, int64_t* tally,
+                int64_t* row_walks) {
     if (!h) return fail(WOST_ERR_INVALID_ARG, "NULL handle");
     if (h->compat != WOST_COMPAT_FIXED)
         return fail(WOST_ERR_UNSUPPORTED, "a tally needs compat=\"fixed\": the reference's source sample does not estimate "
@@ -284,7 +291,10 @@ int wost_solve_range_tally(wost_handle* h, const float* points, int64_t n_points
     if (!h->charges.empty())
         return fail(WOST_ERR_UNSUPPORTED, "a tally rides the source sample: a handle with point sources "
                                           "(wost_set_point_sources) samples none; clear them first");
-    if (h->n_sources != 1 || h->n_wavenumbers > 0 || h->n_models > 0)
+    if (channels && h->n_sources != 1)
+        return fail(WOST_ERR_UNSUPPORTED, "channel maps take one source: the handle scores %d (wost_set_sources); the map "
+                                          "does not depend on f", h->n_sources);
+    if (!channels && (h->n_sources != 1 || h->n_wavenumbers > 0 || h->n_models > 0))
         return fail(WOST_ERR_UNSUPPORTED, "a tally takes one channel: the handle scores %d sources x %d wavenumbers x %d "
                                           "models (wost_set_sources / wost_set_wavenumbers / wost_set_models)",
                     h->n_sources, std::max(h->n_wavenumbers, 1), std::max(h->n_models, 1));
@@ -293,6 +303,9 @@ int wost_solve_range_tally(wost_handle* h, const float* points, int64_t n_points
                                           "0 is enough)");
     if (!h->jit_enabled)
         return fail(WOST_ERR_UNSUPPORTED, "a tally needs the field-specialised kernel (disabled by wost_set_jit)");
+    const int64_t maps = channels ? n_maps : 1;   // sub-rows per replica row
+    if (channels)
+        if (int rc = tally_check_weights(weights, n_maps, h->channels())) return rc;
     if (!tally) return fail(WOST_ERR_INVALID_ARG, "NULL tally");
     if (int rc = tally_grid_check(grid)) return rc;
     if (n_points < 0 || W < 1 || W >= (int64_t(1) << 43))
@@ -304,15 +317,27 @@ int wost_solve_range_tally(wost_handle* h, const float* points, int64_t n_points
     T.scale_log2 = scale_log2;
     if (int rc = tally_limit(W, walk_begin, walk_end, replicas, max_steps, &T.limit)) return rc;
     const int64_t bins = (int64_t)grid->nx * grid->ny + 1;
-    if (n_points > 0 && (replicas > WOST_TALLY_MAX_BYTES / 8 / bins || n_points > WOST_TALLY_MAX_BYTES / 8 / bins / replicas))
+    const int64_t row_cap = WOST_TALLY_MAX_BYTES / 8 / bins / maps;   // replica rows the buffer may hold
+    if (n_points > 0 && (replicas > row_cap || n_points > row_cap / replicas)) {
+        if (channels)
+            return fail(WOST_ERR_INVALID_ARG, "a tally of %lld points x %d replicas x %d maps x %lld bins exceeds %lld bytes",
+                        (long long)n_points, (int)replicas, (int)n_maps, (long long)bins, (long long)WOST_TALLY_MAX_BYTES);
         return fail(WOST_ERR_INVALID_ARG, "a tally of %lld points x %d replicas x %lld bins exceeds %lld bytes",
                     (long long)n_points, (int)replicas, (long long)bins, (long long)WOST_TALLY_MAX_BYTES);
-    const size_t entries = (size_t)(n_points * replicas * bins);
+    }
+    const size_t entries = (size_t)(n_points * replicas * maps * bins);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->d_tally.reserve(std::max<size_t>(entries, 1)));
     HIP_TRY(h->d_tally_flag.reserve(1));
     HIP_TRY(hipMemsetAsync(h->d_tally, 0, sizeof(long long) * entries, h->stream));
     HIP_TRY(hipMemsetAsync(h->d_tally_flag, 0, sizeof(uint32_t), h->stream));
+    if (channels) {   // (a blocking copy of at most 64 floats: done before any launch of the solve)
+        const size_t nw = (size_t)n_maps * (size_t)h->channels();
+        HIP_TRY(h->d_tally_weights.reserve(nw));
+        HIP_TRY(hipMemcpy(h->d_tally_weights, weights, sizeof(float) * nw, hipMemcpyHostToDevice));
+        T.n_maps = n_maps;
+        T.weights = weights;
+    }
 
     SolveRequest rq = whole_request(points, n_points, W, max_steps, eps, seed);
     rq.multi = true;
@@ -343,6 +368,27 @@ int wost_solve_range_tally(wost_handle* h, const float* points, int64_t n_points
     if (row_walks)
         for (int64_t p = 0; p < n_points; ++p) tally_row_walks(walk_begin, walk_end, replicas, row_walks + p * replicas);
     return WOST_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wost_solve_range_tally(wost_handle* h, const float* points, int64_t n_points, int64_t W, int64_t walk_begin,
+                           int64_t walk_end, int32_t max_steps, float eps, uint64_t seed, const wost_tally_grid* grid,
+                           int32_t replicas, int32_t scale_log2, double* block_stats, double* point_stats,
+                           float* walk_values, uint32_t* walk_steps, int64_t* tally, int64_t* row_walks) {
+    return solve_tally(h, points, n_points, W, walk_begin, walk_end, max_steps, eps, seed, grid, replicas, scale_log2,
+                       nullptr, 0, false, block_stats, point_stats, walk_values, walk_steps, tally, row_walks);
+}
+
+int wost_solve_range_tally_channels(wost_handle* h, const float* points, int64_t n_points, int64_t W,
+                                    int64_t walk_begin, int64_t walk_end, int32_t max_steps, float eps, uint64_t seed,
+                                    const wost_tally_grid* grid, int32_t replicas, int32_t scale_log2,
+                                    const float* weights, int32_t n_maps, double* block_stats, double* point_stats,
+                                    float* walk_values, uint32_t* walk_steps, int64_t* tally, int64_t* row_walks) {
+    return solve_tally(h, points, n_points, W, walk_begin, walk_end, max_steps, eps, seed, grid, replicas, scale_log2,
+                       weights, n_maps, true, block_stats, point_stats, walk_values, walk_steps, tally, row_walks);
 }
 
 int wost_solve_range_combined(wost_handle* h, const float* points, int64_t n_points, const int32_t* point_ids,

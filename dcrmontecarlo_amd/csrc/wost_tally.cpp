@@ -63,6 +63,27 @@ int tally_limit(int64_t W, int64_t w0, int64_t w1, int32_t R, int32_t max_steps,
     return WOST_OK;
 }
 
+// The weights of a channel-map solve, float [n_maps][n_channels]: every value finite, no
+// row all zero (its map would be empty).
+int tally_check_weights(const float* weights, int32_t n_maps, int32_t n_channels) {
+    if (n_maps < 1 || n_maps > WOST_TALLY_MAX_MAPS)
+        return fail(WOST_ERR_INVALID_ARG, "channel maps: n_maps = %d, need 1..%d", (int)n_maps, WOST_TALLY_MAX_MAPS);
+    if (n_channels < 1 || n_channels > WOST_MAX_SOURCES)
+        return fail(WOST_ERR_INVALID_ARG, "channel maps: %d channels, need 1..%d", (int)n_channels, WOST_MAX_SOURCES);
+    if (!weights) return fail(WOST_ERR_INVALID_ARG, "channel maps: NULL weights");
+    for (int32_t t = 0; t < n_maps; ++t) {
+        bool any = false;
+        for (int32_t c = 0; c < n_channels; ++c) {
+            const float w = weights[(size_t)t * n_channels + c];
+            if (!std::isfinite(w))
+                return fail(WOST_ERR_INVALID_ARG, "channel maps: weight [%d][%d] is not finite", (int)t, (int)c);
+            any = any || w != 0.0f;
+        }
+        if (!any) return fail(WOST_ERR_INVALID_ARG, "channel maps: row %d of the weights is all zero", (int)t);
+    }
+    return WOST_OK;
+}
+
 }  // namespace wost
 
 using namespace wost;
@@ -89,6 +110,34 @@ int wost_tally_quantize(const float* d, int64_t n, int32_t scale_log2, int64_t l
         ok[i] = tally_quantize(d[i], scale, (float)limit, &q) ? 1 : 0;
         out[i] = q;
     }
+    return WOST_OK;
+}
+
+int wost_tally_check_weights(const float* weights, int32_t n_maps, int32_t n_channels) {
+    return tally_check_weights(weights, n_maps, n_channels);
+}
+
+int wost_tally_weighted(const float* d, int64_t n, int32_t n_channels, const float* weights, int32_t n_maps, float* out) {
+    if (n < 0 || n_channels < 1 || n_maps < 1 || !weights || (n > 0 && (!d || !out)))
+        return fail(WOST_ERR_INVALID_ARG, "bad argument");
+    for (int64_t i = 0; i < n; ++i)
+        for (int32_t t = 0; t < n_maps; ++t)
+            out[i * n_maps + t] = tally_weighted(weights + (size_t)t * n_channels, d + i * n_channels, n_channels);
+    return WOST_OK;
+}
+
+int wost_tally_map_row(int64_t n_points, int32_t replicas, int32_t n_maps, int64_t bins, int64_t point, int64_t walk,
+                       int32_t map, int64_t* entry) {
+    if (!entry) return fail(WOST_ERR_INVALID_ARG, "NULL argument");
+    if (n_points < 1 || replicas < 1 || n_maps < 1 || bins < 1 || point < 0 || point >= n_points || walk < 0 ||
+        walk >= (int64_t(1) << 43) || map < 0 || map >= n_maps)
+        return fail(WOST_ERR_INVALID_ARG, "bad tally shape or index");
+    const int64_t cap = WOST_TALLY_MAX_BYTES / 8;
+    if (bins > cap || n_maps > cap / bins || replicas > cap / bins / n_maps || n_points > cap / bins / n_maps / replicas)
+        return fail(WOST_ERR_INVALID_ARG, "a tally of %lld points x %d replicas x %d maps x %lld bins exceeds %lld bytes",
+                    (long long)n_points, (int)replicas, (int)n_maps, (long long)bins, (long long)WOST_TALLY_MAX_BYTES);
+    const uint32_t base = tally_maps_row((uint64_t)walk, (uint32_t)point, (uint32_t)replicas, (uint32_t)n_maps, (uint32_t)bins);
+    *entry = (int64_t)(base + (uint32_t)map * (uint32_t)bins);
     return WOST_OK;
 }
 

@@ -53,6 +53,9 @@ struct KernelVariant {
                                      // (WOST_POINT_LIST; wost_solve_range_points)
     bool tally = false;              // the source samples' deposits go to WalkArgs::tally
                                      // (WOST_TALLY; wost_solve_range_tally)
+    int tally_maps = 0;              // T: weighted channel maps a step deposits (WOST_TALLY_MAPS;
+                                     // wost_solve_range_tally_channels); 0: none. Not `tally`: that one stays
+                                     // the one-channel kernel
 };
 
 inline bool operator==(const KernelVariant& a, const KernelVariant& b) {
@@ -61,7 +64,7 @@ inline bool operator==(const KernelVariant& a, const KernelVariant& b) {
            a.block == b.block &&
            a.global_polylines == b.global_polylines && a.tree_stage == b.tree_stage && a.exact_trig == b.exact_trig &&
            a.dirichlet_tree == b.dirichlet_tree && a.point_list == b.point_list &&
-           a.tally == b.tally;
+           a.tally == b.tally && a.tally_maps == b.tally_maps;
 }
 
 }  // namespace wost

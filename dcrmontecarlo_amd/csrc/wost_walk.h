@@ -142,6 +142,14 @@ struct WalkArgs {
     int32_t tally_nx, tally_ny;
     int32_t tally_replicas;
     float tally_scale, tally_limit;
+    // channel maps (wost_solve_range_tally_channels; read only by kernels built with
+    // WOST_TALLY_MAPS T): tally is then [n_points][tally_replicas][T][bins] and tally_weights the
+    // float [T][C] combination weights of the launch's C channels, tally_n_weights = T * C of
+    // them. Run-time data behind a pointer (wave-uniform scalar loads through the constant
+    // address space), so one kernel per (problem, channels, T) serves every combination. Null /
+    // 0 otherwise.
+    const float* tally_weights;
+    int32_t tally_n_weights;
 };
 
 // The Dirichlet polyline's tree as poly_distance_tree reads it (records and vertices through
@@ -953,25 +961,56 @@ WOST_HD uint32_t tally_row_base(const WalkArgs& A, uint64_t wid, uint64_t pid) {
     const uint32_t row = (uint32_t)(i / (uint64_t)WOST_BLOCK_WALKS) % (uint32_t)A.tally_replicas;
     return ((uint32_t)pid * (uint32_t)A.tally_replicas + row) * (uint32_t)(A.tally_nx * A.tally_ny + 1);
 }
-// One deposit d at the sample (yx, yy): a no-return 64-bit integer add at device scope to the
+// One deposit d at the sample (yx, yy) (tally_deposit; tally_add: at an entry already found):
+// a no-return 64-bit integer add at device scope to the
 // sample's bin of the row that starts at entry `base`, so that the sums do not depend on the
 // order of arrival. A deposit that does not fit (tally_quantize) is not added and sets the
 // flag word (q is 0 then): the host then fails the solve. The word keeps the largest E + 1
 // seen, E the float32 exponent field of the scaled deposit (|d * scale| < 2^(E - 126); 255:
 // infinite or NaN), so that the host can name a quantum under which every deposit fits.
-__device__ __forceinline__ void tally_deposit(const WalkArgs& A, uint32_t base, float yx, float yy, float d) {
-    const int cell = tally_cell(yx, yy, A.tally_x0, A.tally_y0, A.tally_dx, A.tally_dy, A.tally_inv_dx,
-                                A.tally_inv_dy, A.tally_nx, A.tally_ny);
+__device__ __forceinline__ void tally_add(const WalkArgs& A, size_t entry, float d) {
     long long q;
     const bool bad = !tally_quantize(d, A.tally_scale, A.tally_limit, &q);
     if (WOST_ANY(bad)) {
         if (bad) atomicMax(A.tally_flag, ((__builtin_bit_cast(uint32_t, d * A.tally_scale) >> 23) & 0xffu) + 1u);
     }
 #if defined(__HIP_DEVICE_COMPILE__)
-    (void)__hip_atomic_fetch_add(A.tally + ((size_t)base + (size_t)cell), q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(A.tally + entry, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #else
-    A.tally[(size_t)base + (size_t)cell] += q;
+    A.tally[entry] += q;
 #endif
+}
+__device__ __forceinline__ void tally_deposit(const WalkArgs& A, uint32_t base, float yx, float yy, float d) {
+    const int cell = tally_cell(yx, yy, A.tally_x0, A.tally_y0, A.tally_dx, A.tally_dy, A.tally_inv_dx,
+                                A.tally_inv_dy, A.tally_nx, A.tally_ny);
+    tally_add(A, (size_t)base + (size_t)cell, d);
+}
+// WOST_TALLY_MAPS T (1..WOST_TALLY_MAX_MAPS; generated kernels of
+// wost_solve_range_tally_channels, KernelVariant::tally_maps): the tally of a launch with NM *
+// NK channels (one source, no point charges, no recorder, no walk pools). The refill finds the
+// first of the walk's T sub-rows; a step that is not clipped forms, per map, the weighted
+// combination of the deposits a source f == 1 would score on each channel (tally_weighted,
+// WalkArgs::tally_weights) and adds it to the sample's bin of that map's sub-row: one cell
+// computation, T quantisations, T adds. WOST_TALLY stays the one-channel tally; not both.
+#ifndef WOST_TALLY_MAPS
+#define WOST_TALLY_MAPS 0
+#endif
+// (row t of the weights, as scalar loads from constant memory)
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) float* TallyWeightRow;
+#else
+typedef const float* TallyWeightRow;
+#endif
+template <int T, int C>
+__device__ __forceinline__ void tally_deposit_maps(const WalkArgs& A, uint32_t base, float yx, float yy,
+                                                   const float (&d)[C]) {
+    const int cell = tally_cell(yx, yy, A.tally_x0, A.tally_y0, A.tally_dx, A.tally_dy, A.tally_inv_dx,
+                                A.tally_inv_dy, A.tally_nx, A.tally_ny);
+    const uint32_t bins = (uint32_t)(A.tally_nx * A.tally_ny + 1);
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+        tally_add(A, (size_t)(base + (uint32_t)t * bins) + (size_t)cell,
+                  tally_weighted((TallyWeightRow)A.tally_weights + t * C, d, C));
 }
 // Walk pools (TREE kernels): see the exchange in walk_body. WOST_TREE_POOL 0 compiles
 // them out; WOST_POOL_MIN_PUSH: fewest mismatched walks a wave parks at once.
@@ -1096,6 +1135,10 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                   "point sources need compat=\"fixed\", a source mode, no recorder, at most WOST_MAX_POINT_CHARGES charges");
     static_assert(!WOST_TALLY || (SRC && NS == 1 && NK == 1 && NM == 1 && PC == 0 && !REC),
                   "a tally needs a source mode, one channel, no point charges, no recorder");
+    static_assert(!WOST_TALLY_MAPS || (SRC && NS == 1 && PC == 0 && !REC && !WOST_TALLY && WOST_TALLY_MAPS >= 1 &&
+                                       WOST_TALLY_MAPS <= WOST_TALLY_MAX_MAPS),
+                  "channel maps need a source mode, one source, no point charges, no recorder, at most "
+                  "WOST_TALLY_MAX_MAPS maps and no WOST_TALLY beside them");
     constexpr int NW = NM * NK;   // weights: wc = m * NK + j
     constexpr int NC = NW * NS;   // channels: c = (m * NK + j) * NS + s
     // (a Dirichlet-tree kernel reads the vertices it needs through global loads)
@@ -1149,7 +1192,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     }
     // this workgroup's walk pools (header: lock, walks parked near, walks parked far)
     // (a parked walk holds no tally row: tally kernels run without pools)
-    uint32_t* const pool = (TREE && WOST_TREE_POOL && !WOST_TALLY && NK == 1 && PC == 0 && NM == 1 && A.pool != nullptr)
+    uint32_t* const pool = (TREE && WOST_TREE_POOL && !WOST_TALLY && !WOST_TALLY_MAPS && NK == 1 && PC == 0 && NM == 1 && A.pool != nullptr)
                                ? A.pool + (size_t)blockIdx.x * (size_t)A.pool_wg_words : nullptr;
     if (pool != nullptr && threadIdx.x < 4) pool[threadIdx.x] = 0u;
     __syncthreads();
@@ -1208,8 +1251,8 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
     bool onB = false;           // onBoundary
     float phi = 0.f;            // atan2 of currentNormal (:228), set when onB
     int xcode = 0;              // (PC > 0) boundary_code of the current point: its segment and inward side
-#if WOST_TALLY
-    uint32_t trow = 0u;         // first entry of this walk's tally row (tally_row_base)
+#if WOST_TALLY || WOST_TALLY_MAPS
+    uint32_t trow = 0u;         // first entry of this walk's tally row (tally_row_base; tally_maps_row)
 #endif
     float ax[NM];               // alpha(current_point), cached (one per model)
 #pragma unroll
@@ -1396,6 +1439,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 if (WOST_PHILOX_AHEAD) rn_ahead = philox_draw(pw, 0u, A.key0, A.key1);
 #if WOST_TALLY
                 trow = tally_row_base(A, wid, pid);
+#elif WOST_TALLY_MAPS
+                trow = tally_maps_row(wid - pid * (uint64_t)A.walks_per_point, (uint32_t)pid, (uint32_t)A.tally_replicas,
+                                      (uint32_t)WOST_TALLY_MAPS, (uint32_t)(A.tally_nx * A.tally_ny + 1));
 #endif
                 const float2 q = A.points[pid];
                 px = q.x; py = q.y;
@@ -1766,6 +1812,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                         c = f * ((r * r) / 4.0f);                        // :256, utils.py:61
 #if WOST_TALLY   // what f == 1.0f scores here: (1.0f * gnorm) is gnorm, 1.0f * (r * r / 4) is r * r / 4
                     tally_deposit(A, trow, yx, yy, DELTA ? (gnorm * f_rsq(aj.v * ax[0])) * w[0] : (r * r) / 4.0f);
+#elif WOST_TALLY_MAPS   // one channel (one wavenumber, no models): the same deposit, T weights of it
+                    const float td[1] = {DELTA ? (gnorm * f_rsq(aj.v * ax[0])) * w[0] : (r * r) / 4.0f};
+                    tally_deposit_maps<WOST_TALLY_MAPS, 1>(A, trow, yx, yy, td);
 #endif
                 }
                 total[0] = total[0] + c;                                 // :258
@@ -1775,9 +1824,16 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                 if constexpr (NS == 1) fv[0] = fld.f(yx, yy);
                 else fld.f_multi(yx, yy, fv);
                 const float q = DELTA ? 0.0f : ((r * r) / 4.0f);
+#if WOST_TALLY_MAPS   // what f == 1.0f scores on channel m * NK + j: (1.0f * gnorm) is gnorm
+                float td[NW];
+#endif
 #pragma unroll
                 for (int m = 0; m < NM; ++m) {
                     const float sa = DELTA ? f_rsq((NM > 1 ? ajm[m].v : aj.v) * ax[m]) : 0.0f;
+#if WOST_TALLY_MAPS
+#pragma unroll
+                    for (int j = 0; j < NK; ++j) td[m * NK + j] = DELTA ? (gnorm * sa) * w[m * NK + j] : q;
+#endif
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
                         const float fg = DELTA ? ((fv[s] * gnorm) * sa) : fv[s] * q;
@@ -1788,6 +1844,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& A, const F& fld, unsig
                         }
                     }
                 }
+#if WOST_TALLY_MAPS
+                tally_deposit_maps<WOST_TALLY_MAPS, NW>(A, trow, yx, yy, td);
+#endif
             } else {
 #pragma unroll
                 for (int c = 0; c < NC; ++c) total[c] = total[c] + 0.0f;

@@ -224,7 +224,7 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
                   sigma=None, alpha=None, *, sigma_bar: float | None = None, compat: str = "reference",
                   sources=None, n_wavenumbers: int = 0, models=None, options: dict | None = None,
                   dirichlet_tree: int | None = None, dirichlet_tree_leaf: int = 0, point_list: bool = False,
-                  tally: bool = False) -> str:
+                  tally: bool = False, tally_maps: int = 0) -> str:
     """HIP source of the field-specialised walk kernel a WostSolver_2D with these
     arguments would compile (no device needed; wost_kernel_source). sources: the fields
     of a multi-source solve (solve_sources; wost_kernel_source_sources); n_wavenumbers: the
@@ -238,7 +238,13 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
     a solve with a point list launches (solve_range(point_ids=...), solve_to_tolerance;
     wost_kernel_source_point_list; with sources, wavenumbers and models, not with options or
     dirichlet_tree); tally: the kernel solve_greens_map launches (wost_kernel_source_tally;
-    compat="fixed" and a source, and none of the other keywords: a tally takes one channel)."""
+    compat="fixed" and a source, and none of the other keywords: a tally takes one channel);
+    tally_maps: the kernel solve_greens_maps launches for that many maps (1..4;
+    wost_kernel_source_tally_channels; compat="fixed" and a source; with n_wavenumbers and
+    models, not with tally or the other keywords)."""
+    if tally_maps and (tally or point_list or options or dirichlet_tree is not None or sources):
+        raise ValueError("tally_maps: with n_wavenumbers and models only -- not together with tally, sources, "
+                         "point_list, options or dirichlet_tree")
     if tally and (point_list or options or dirichlet_tree is not None or sources or n_wavenumbers or models is not None):
         raise ValueError("tally: one channel only -- not together with sources, n_wavenumbers, models, point_list, "
                          "options or dirichlet_tree")
@@ -283,6 +289,10 @@ def kernel_source(dirichletBoundary, dirichletBoundaryFunction=None, neumannBoun
             ctypes.byref(prob), int(dirichlet_tree), int(dirichlet_tree_leaf), 0, 0, buf, cap, ctypes.byref(n))
     if tally:
         call = lambda buf, cap: _lib.lib.wost_kernel_source_tally(ctypes.byref(prob), buf, cap, ctypes.byref(n))
+    if tally_maps:
+        marr, nm = (None, 0) if models is None else (marr, len(models))
+        call = lambda buf, cap: _lib.lib.wost_kernel_source_tally_channels(
+            ctypes.byref(prob), marr, nm, int(n_wavenumbers), int(tally_maps), buf, cap, ctypes.byref(n))
     _lib.check(call(None, 0), "wost_kernel_source")
     buf = ctypes.create_string_buffer(n.value + 1)
     _lib.check(call(buf, n.value + 1), "wost_kernel_source")
@@ -640,6 +650,139 @@ class WostSolver_2D:
         gm = GreensMap(tally[:, :, :-1].reshape(n, R, g.ny, g.nx).copy(), tally[:, :, -1].copy(), rows, 2.0 ** -s, g,
                        _like(u, solvePoints), st)
         return (gm, wv, ws) if return_walks else gm
+
+    def _launch_greens_maps(self, p, grid, w, nWalks, w0, w1, maxSteps, eps, seed, R, s, want_walks):
+        """One wost_solve_range_tally_channels launch: the maps of the rows ``w`` (float32
+        [T <= 4, C]) at scale 2^s. Returns (tally int64 [N, R, T, bins], row_walks int64
+        [N, R], point sums float64 [N, 2C+1], walk values float32 [N, walks, C] or None, walk
+        steps uint32 [N, walks] or None)."""
+        from ..greens_map import _c_grid
+
+        n, (T, C) = p.shape[0], w.shape
+        cg = _c_grid(grid)
+        tally = np.zeros((n, R, T, grid.nx * grid.ny + 1), np.int64)
+        rows = np.zeros((n, R), np.int64)
+        sums = np.zeros((n, 2 * C + 1), np.float64)
+        nw = max(w1 - w0, 0)
+        wv = np.empty((n, nw, C), np.float32) if want_walks else None
+        ws = np.empty((n, nw), np.uint32) if want_walks else None
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        _lib.check(_lib.lib.wost_solve_range_tally_channels(
+            self._h, _lib.fptr(p), n, nWalks, w0, w1, int(maxSteps), float(eps), _lib.seed64(seed), ctypes.byref(cg),
+            R, s, _lib.fptr(w), T, None, _lib.dptr(sums), _lib.fptr(wv), _lib.u32ptr(ws), tally.ctypes.data_as(i64),
+            rows.ctypes.data_as(i64)), "WostSolver_2D.solve_greens_maps")
+        self.last_timing = self.timing()
+        return tally, rows, sums, wv, ws
+
+    def _default_tally_scale(self, nWalks, w0, w1, R, maxSteps) -> int:
+        s = ctypes.c_int32(0)
+        _lib.check(_lib.lib.wost_tally_default_scale(self._h, nWalks, w0, w1, R, int(maxSteps), ctypes.byref(s)),
+                   "solve_greens_maps")
+        return int(s.value)
+
+    def solve_greens_maps(self, solvePoints, grid, weights, nWalks=1000, maxSteps=1000, eps=1e-4, *, seed: int = 0,
+                          replicas: int = 8, quantum: float | None = None, walk_begin: int = 0,
+                          walk_end: int | None = None, return_channels: bool = False, return_walks: bool = False):
+        """``solve_greens_map`` for a solver with wavenumbers and / or models set
+        (set_wavenumbers, set_models; wost_solve_range_tally_channels, DESIGN.md 7f "Channel
+        maps"): a list of T :class:`~dcrmontecarlo_amd.greens_map.GreensMap`, map t the tally
+        of the combination ``weights[t]`` of the C installed channels (c = m * K + j, model
+        major), formed per deposit on the device. ``weights`` is [T, C] (a single row [C] is
+        one map) and is **rounded to float32**: the kernel forms v_t = sum_c fl(w[t, c] * d_c)
+        in float32, channels ascending, every product and sum rounded on its own, zero weights
+        skipped -- a unit row gives, integer for integer, the solve_greens_map of that
+        channel's own problem on this sigma_bar. No row may be all zero or hold a non-finite
+        value.
+
+        One launch keeps at most 4 maps; more rows are **chunked over launches of at most 4,
+        and each chunk walks again** -- the same walks (same seed), so every row's integers
+        are what a single launch would give, at the cost of one walk set per chunk
+        (``last_timing`` is the last chunk's). ``quantum`` None: solve_greens_map's bound on
+        one channel's deposit, over the smallest alpha of all installed models, times
+        max_t sum_c |w[t, c]| (formed here, in the facade). Every map of the call shares the
+        quantum. The maps' ``u`` / ``stats`` stay None: the channels' own solve --
+        bit for bit solve_range's for the same solver -- comes with return_channels=True as
+        (maps, u float32 [N, C], SolveStats with mean / stderr [N, C]); return_walks=True also
+        appends (values float32 [N, walks, C], steps uint32 [N, walks]).
+        compat="fixed" only, no point sources, no extra sources; replicas, walk_begin /
+        walk_end and the Neumann start as in solve_greens_map."""
+        from ..greens_map import GreensMap, as_grid
+
+        if self.compat != "fixed":
+            raise NotImplementedError("solve_greens_maps needs compat=\"fixed\": the reference's source sample does not "
+                                      "estimate the integral of G f (quirks Q3, Q13)")
+        if self.point_sources is not None:
+            raise NotImplementedError("solve_greens_maps rides the source sample: the solver has point sources "
+                                      "(set_point_sources) set; clear them first")
+        C = self.num_channels()
+        if C != max(self.num_models, 1) * (1 if self.wavenumbers is None else self.wavenumbers.size):
+            raise NotImplementedError(f"solve_greens_maps takes one source: the handle scores {C} channels (extra "
+                                      "sources are installed); the map does not depend on f")
+        w = np.asarray(_np(weights), np.float64)
+        with np.errstate(over="ignore"):   # (a weight beyond float32 becomes inf and is refused below)
+            w = np.ascontiguousarray(np.atleast_2d(w).astype(np.float32))   # the kernel's weights: float32
+        if w.ndim != 2 or w.shape[1] != C or w.shape[0] < 1:
+            raise ValueError(f"weights must have shape [T, {C}] for the {C} installed channels, got {w.shape}")
+        if not np.isfinite(w).all() or not (w != 0).any(axis=1).all():
+            raise ValueError("weights: every value finite (as float32) and no row all zero")
+        p = _points_np(solvePoints)
+        n = p.shape[0]
+        nWalks = _walk_count(nWalks)
+        w0, w1 = int(walk_begin), nWalks if walk_end is None else int(walk_end)
+        R = int(replicas)
+        g = as_grid(grid)
+        if R < 1:
+            raise ValueError(f"replicas must be >= 1 (got {replicas})")
+        if g.nx < 1 or g.ny < 1:
+            raise ValueError("the grid needs nx, ny >= 1")
+        bins = g.nx * g.ny + 1
+        cap = _lib.WOST_TALLY_MAX_MAPS
+        if n * R * min(w.shape[0], cap) * bins * 8 > _lib.WOST_TALLY_MAX_BYTES:
+            raise ValueError(f"a tally of {n} points x {R} replicas x {min(w.shape[0], cap)} maps x {bins} bins exceeds "
+                             f"{_lib.WOST_TALLY_MAX_BYTES} bytes: fewer points per call, replicas, rows or cells")
+
+        @contextlib.contextmanager
+        def zero_source():   # the tally rides the source sample: a constant 0 for the call
+            wf, keep = _lib.make_field(const(0.0))
+            _lib.check(_lib.lib.wost_set_field(self._h, _lib.SLOT_SOURCE, ctypes.pointer(wf)), "solve_greens_maps")
+            try:
+                yield
+            finally:
+                _lib.check(_lib.lib.wost_set_field(self._h, _lib.SLOT_SOURCE, None), "solve_greens_maps")
+
+        maps, first = [], None
+        with (zero_source() if self.source is None else contextlib.nullcontext()):
+            if quantum is None:
+                gain = float(np.abs(w.astype(np.float64)).sum(axis=1).max())
+                s = self._default_tally_scale(nWalks, w0, w1, R, maxSteps) - int(np.ceil(np.log2(gain)))
+                s = max(-100, min(100, s))
+            else:
+                if not (quantum > 0 and np.isfinite(quantum)):
+                    raise ValueError(f"quantum must be positive and finite (got {quantum})")
+                s = -int(np.floor(np.log2(float(quantum))))
+            for t0 in range(0, w.shape[0], cap):   # every chunk walks again: the same walks
+                tally, rows, sums, wv, ws = self._launch_greens_maps(p, g, np.ascontiguousarray(w[t0:t0 + cap]), nWalks,
+                                                                      w0, w1, maxSteps, eps, seed, R, s,
+                                                                      return_walks and first is None)
+                if first is None:
+                    first = (sums, wv, ws)
+                for t in range(tally.shape[2]):
+                    maps.append(GreensMap(tally[:, :, t, :-1].reshape(n, R, g.ny, g.nx).copy(),
+                                          tally[:, :, t, -1].copy(), rows.copy(), 2.0 ** -s, g))
+        sums, wv, ws = first
+        self.last_point_sums = sums
+        out = [maps]
+        if return_channels:
+            nw = max(w1 - w0, 1)
+            mean, se, _ = tolerance_rule(sums, nw, 0.0, 0.0)   # [C, N]
+            tm = self.last_timing
+            out += [_like(np.ascontiguousarray(mean.T.astype(np.float32)), solvePoints),
+                    SolveStats(mean=mean.T, stderr=se.T, mean_steps=sums[:, -1] / nw, walks=nw,
+                               total_steps=int(tm["total_steps"]), kernel_ms=tm["walk_kernel_ms"],
+                               total_ms=tm["total_ms"])]
+        if return_walks:
+            out += [wv, ws]
+        return maps if len(out) == 1 else tuple(out)
 
     def _combination_weights(self, weights) -> np.ndarray:
         """``weights`` as contiguous float64 [L, C] for the C installed channels (ValueError

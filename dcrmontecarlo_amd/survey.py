@@ -898,3 +898,27 @@ def run_wenner_survey(sc: Scenario, alpha_bg: float, n_walks: int, a: int = 1, w
     dh = DipoleData(mean[1][q, M] - mean[1][q, N], np.sqrt(se[1][q, M] ** 2 + se[1][q, N] ** 2))
     return WennerSurveyResult(quad, dm, dh, apparent_resistivity(dm, dh, 1.0 / alpha_bg), steps, launches, kms,
                               acc[0][2] + acc[1][2], phase_ms)
+
+
+def paired_difference_map(solver, model, background, points, grid, **solve_kw):
+    """The change of a Green's function map under a model perturbation, G_model -
+    G_background, from shared walks (DESIGN.md 7f "Channel maps"; ``paired_difference`` for
+    maps): the two (sigma, alpha) models are installed together (``set_models([background,
+    model])``), and one launch keeps the rows [-1, +1], [1, 0] and [0, 1] of the two channels.
+    Returns (difference, background map, model map), three GreensMaps of the same walks,
+    quantum and grid. The difference is formed per deposit in float32 before it is rounded to
+    the quantum, so its integers equal model - background only to within the roundings
+    (DESIGN.md 7f gives the bound); its replica rows carry the paired standard error, which
+    two separate maps cannot give. ``solver``: compat="fixed", delta tracking, a sigma_bar
+    that covers both models (``sigma_bar_for_models``); its models are restored afterwards.
+    ``solve_kw``: as ``WostSolver_2D.solve_greens_maps``."""
+    if solver.wavenumbers is not None:
+        raise NotImplementedError("paired_difference_map takes the solver's own operator: clear its wavenumbers "
+                                  "(set_wavenumbers(None)), or pass solve_greens_maps the rows of the 2 K channels")
+    saved = getattr(solver, "models", None)
+    solver.set_models([background, model])
+    try:
+        diff, bg, md = solver.solve_greens_maps(points, grid, [[-1.0, 1.0], [1.0, 0.0], [0.0, 1.0]], **solve_kw)
+    finally:
+        solver.set_models(saved)
+    return diff, bg, md

@@ -347,3 +347,35 @@ def run_dipole_dipole_survey_25d(sc: Scenario, n_walks: int, n_max: int = 4, wid
 
     return _run_25d(sc, quad, [0, 1], lambda q: (q[:, 3], q[:, 2]), factor, n_walks, width, n_k, groups, seed,
                     device, compat, solvers, dx, (n_max + 2) * dx, electrodes, device_reduce)
+
+
+def greens_section_25d(solver, points, grid, r_min: float, r_max: float, n: int | None = None, *,
+                       per_wavenumber: bool = False, **solve_kw):
+    """The 2.5-D potential section of a point electrode (DESIGN.md 7f "Channel maps"): the map
+    of sum_j (w_j / 2) G_{k_j}(x_p, .) for every query point x_p, the wavenumbers and weights
+    (k, w) of ``wavenumber_quadrature(r_min, r_max, n)`` (``n`` None: 4, 6 or 8 from r_max /
+    r_min, as the surveys choose it), formed per deposit on the device in one launch
+    (``WostSolver_2D.solve_greens_maps`` with the single row w / 2: the I / 2 convention of
+    DESIGN.md 7a for a point current). By self-adjointness the row of x_p is the 3-D
+    potential, per unit point current at x_p, in the plane of the profile, averaged over each
+    cell -- for distances within [r_min, r_max] of the electrode, where the quadrature holds.
+    Returns (GreensMap, k, w); with ``per_wavenumber`` (GreensMap, [GreensMap of G_{k_j}] * K,
+    k, w), the unit rows (chunked over launches of at most 4 maps, each walking again).
+
+    ``solver``: a compat="fixed" WostSolver_2D with delta tracking whose sigma_bar covers
+    max k^2 (``sigma_bar_for``); its wavenumbers are set for the call and restored afterwards.
+    ``solve_kw``: nWalks, maxSteps, eps, seed, replicas, quantum, walk_begin, walk_end. The
+    float32 rounding of w / 2 is the kernel's (solve_greens_maps). A query point ON the
+    Neumann polyline -- a surface electrode -- starts as every field-source solve starts it
+    (DESIGN.md 9 item 0a); this function does not address that."""
+    if n is None:
+        n = 4 if r_max <= 3.0 * r_min else 6 if r_max <= 12.0 * r_min else 8
+    k, w = wavenumber_quadrature(r_min, r_max, n)
+    rows = [w / 2.0] + ([row for row in np.eye(k.size)] if per_wavenumber else [])
+    saved = solver.wavenumbers
+    solver.set_wavenumbers(k)
+    try:
+        maps = solver.solve_greens_maps(points, grid, np.asarray(rows, np.float64), **solve_kw)
+    finally:
+        solver.set_wavenumbers(saved)
+    return (maps[0], maps[1:], k, w) if per_wavenumber else (maps[0], k, w)

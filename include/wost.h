@@ -487,7 +487,8 @@ int wost_tally_limit(int64_t walks_per_point, int64_t walk_begin, int64_t walk_e
  * one at which 2^16 times a cheap bound B on one deposit stays below wost_tally_limit. B is
  * diag^2 / 4 of the Dirichlet polyline's bounding box without delta tracking (a deposit is
  * r^2 / 4) and 1 / (sigma_bar * min alpha) with it, alpha sampled on the 50 x 50 grid that
- * the sigma_bar estimate samples. B is an estimate -- it leaves out the walk's weight, which
+ * the sigma_bar estimate samples (with models installed, wost_set_models: the smallest over all
+ * of them). B is an estimate -- it leaves out the walk's weight, which
  * a sigma_bar below sigma' lets grow without bound; the solve's check is the guarantee. */
 int wost_tally_default_scale(const wost_handle* h, int64_t walks_per_point, int64_t walk_begin, int64_t walk_end,
                              int32_t replicas, int32_t max_steps, int32_t* scale_log2);
@@ -522,6 +523,63 @@ int wost_solve_range_tally(wost_handle* h, const float* points, int64_t n_points
                            double* block_stats, double* point_stats,
                            float* walk_values, uint32_t* walk_steps,
                            int64_t* tally, int64_t* row_walks);
+
+/* Channel maps (DESIGN.md 7f "Channel maps"): the tally of a handle with wavenumbers and / or
+ * models set. A launch scores C = wost_num_channels(h) channels, c = m * NK + j (model major);
+ * at a step whose source sample is not clipped, channel c would score for a source f == 1
+ *      d_c = (G_norm * rsq(alpha_m(y) alpha_m(x))) * w[m * NK + j]
+ * and the solve keeps n_maps maps, map t a weighted combination of the channels formed per
+ * deposit in the kernel, in float32, product and sum each rounded on its own (no FMA):
+ *      v_t = 0;  for c ascending:  if (weights[t][c] != 0)  v_t = v_t + weights[t][c] * d_c
+ * A zero weight skips its channel (whatever it holds: a unit row is d_c itself), so the map
+ * of a unit row is bit for bit the one-channel tally of that channel's own problem. One add
+ * per map and step: the 2.5-D section sum_j w_j G_{k_j} costs what one map costs. */
+#define WOST_TALLY_MAX_MAPS 4
+
+/* 0 when weights [n_maps][n_channels] are accepted by wost_solve_range_tally_channels:
+ * 1 <= n_maps <= WOST_TALLY_MAX_MAPS, 1 <= n_channels <= WOST_MAX_SOURCES, non-NULL, every
+ * value finite, no row all zero. WOST_ERR_INVALID_ARG with a message otherwise. Host only. */
+int wost_tally_check_weights(const float* weights, int32_t n_maps, int32_t n_channels);
+/* The kernels' combination, on the host: d is [n][n_channels] deposits, out [n][n_maps], out[i][t]
+ * = v_t of row i by the rule above (wost_device.h tally_weighted: the kernels' own text).
+ * Only n_maps >= 1, n_channels >= 1 and the pointers are checked: any weights, any n_maps. Host only. */
+int wost_tally_weighted(const float* d, int64_t n, int32_t n_channels, const float* weights, int32_t n_maps,
+                        float* out);
+/* The entry of the tally buffer [n_points][replicas][n_maps][bins] at which map `map` of walk
+ * `walk` (its index in [0, walks_per_point)) of point `point` starts, by the kernels' own 32-bit
+ * arithmetic (wost_device.h tally_maps_row: the refill's). The buffer must hold at most
+ * WOST_TALLY_MAX_BYTES (WOST_ERR_INVALID_ARG otherwise). Host only. */
+int wost_tally_map_row(int64_t n_points, int32_t replicas, int32_t n_maps, int64_t bins, int64_t point, int64_t walk,
+                       int32_t map, int64_t* entry);
+
+/* wost_solve_range_tally for a handle with wavenumbers and / or models (or neither: C = 1).
+ * The ordinary outputs are wost_solve_range's for the same handle, all C channels, bit for
+ * bit (rows of 2 C + 1 doubles, C values per walk).
+ *   weights   float [n_maps][C]
+ *   tally     [n_points][replicas][n_maps][nx * ny + 1] int64
+ *   row_walks [n_points][replicas] int64
+ * scale_log2 is the caller's: wost_tally_default_scale bounds one channel's deposit (over the
+ * smallest alpha of all installed models); the facade (WostSolver_2D.solve_greens_maps)
+ * multiplies that bound by max_t sum_c |weights[t][c]|. A v_t that does not fit raises the
+ * flag as a deposit of wost_solve_range_tally does: WOST_ERR_INVALID_ARG, a scale that fits
+ * is named, no tally is written.
+ *   WOST_ERR_UNSUPPORTED  a compat="reference" handle; point charges; more than one source
+ *                         (the map does not depend on f); the field-specialised kernel
+ *                         disabled or not buildable
+ *   WOST_ERR_INVALID_ARG  no source field; n_maps outside [1, WOST_TALLY_MAX_MAPS]; NULL,
+ *                         non-finite or all-zero weight rows; a tally buffer (with its factor
+ *                         n_maps) above WOST_TALLY_MAX_BYTES; and everything
+ *                         wost_solve_range_tally refuses about grids, walks and scales
+ * The kernel is one of its own per (handle, n_maps) (WOST_TALLY_MAPS); the weights are
+ * run-time data. Segment-tree launches run without walk pools. */
+int wost_solve_range_tally_channels(wost_handle* h, const float* points, int64_t n_points,
+                                    int64_t walks_per_point, int64_t walk_begin, int64_t walk_end,
+                                    int32_t max_steps, float eps, uint64_t seed,
+                                    const wost_tally_grid* grid, int32_t replicas, int32_t scale_log2,
+                                    const float* weights, int32_t n_maps,
+                                    double* block_stats, double* point_stats,
+                                    float* walk_values, uint32_t* walk_steps,
+                                    int64_t* tally, int64_t* row_walks);
 
 /* Weighted channel combinations, reduced on the device (no reference counterpart; DESIGN.md
  * 7e). The C = wost_num_channels(h) channels of a launch share their walks and are
@@ -801,6 +859,15 @@ int wost_kernel_source_point_list(const wost_problem* problem, const wost_model*
  * else of the source differs. With the solve's refusals that need no device
  * (compat="reference": WOST_ERR_UNSUPPORTED; no source field: WOST_ERR_INVALID_ARG). Host only. */
 int wost_kernel_source_tally(const wost_problem* problem, char* out, int64_t capacity, int64_t* length);
+
+/* wost_kernel_source_models' kernel (models NULL / n_models 0: none; n_wavenumbers as there)
+ * as wost_solve_range_tally_channels launches it with n_maps maps (WOST_TALLY_MAPS n_maps):
+ * nothing else of the source differs. With that solve's refusals that need no device
+ * (compat="reference": WOST_ERR_UNSUPPORTED; no source field, n_maps outside
+ * [1, WOST_TALLY_MAX_MAPS]: WOST_ERR_INVALID_ARG). Host only. */
+int wost_kernel_source_tally_channels(const wost_problem* problem, const wost_model* models, int32_t n_models,
+                                      int32_t n_wavenumbers, int32_t n_maps, char* out, int64_t capacity,
+                                      int64_t* length);
 
 /* The same for a handle with n_charges point charges in n_sources source channels
  * (wost_set_point_sources; the problem must have no source field) and n_wavenumbers

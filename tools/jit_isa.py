@@ -9,6 +9,8 @@ Usage: python tools/jit_isa.py dcr_dipole [--out build/jit] [--show] [--votes] [
        [--models M]           (set_models: the scenario's fields, a constant background, then perturbed copies)
        [--point-list]         (the kernel of solve_range(point_ids=...) / solve_to_tolerance: WOST_POINT_LIST)
        [--tally]              (the kernel of solve_greens_map: WOST_TALLY; compat="fixed", the scenario's own source)
+       [--tally-maps T]       (the kernel of solve_greens_maps with T maps: WOST_TALLY_MAPS; compat="fixed", with
+                               --wavenumbers / --models)
        [--compat fixed]       (the plain kernel under compat="fixed": what --tally is compared with)"""
 import argparse
 import collections
@@ -102,12 +104,16 @@ def main():
                     help="the point-list kernel (solve_range(point_ids=...), solve_to_tolerance); not with --point-charges")
     ap.add_argument("--tally", action="store_true",
                     help="the tally kernel (solve_greens_map; compat=\"fixed\"); not with the channel options")
+    ap.add_argument("--tally-maps", type=int, default=0,
+                    help="T: the channel-map kernel (solve_greens_maps; compat=\"fixed\"); with --wavenumbers / --models")
     ap.add_argument("--compat", default="reference", choices=("reference", "fixed"), help="the kernel's estimators")
     a = ap.parse_args()
     if a.point_list and a.point_charges:
         ap.error("--point-list: not together with --point-charges")
     if a.tally and (a.point_list or a.point_charges or a.sources or a.wavenumbers or a.models):
         ap.error("--tally: one channel only")
+    if a.tally_maps and (a.tally or a.point_list or a.point_charges or a.sources):
+        ap.error("--tally-maps: with --wavenumbers and --models only")
     if a.waves:
         os.environ["WOST_JIT_WAVES"] = a.waves
     from dcrmontecarlo_amd import scenarios as S
@@ -131,11 +137,13 @@ def main():
     else:
         src = sc.kernel_source(n_wavenumbers=a.wavenumbers, **({"sources": [sc.f * (1.0 + k) for k in range(a.sources)]}
                                                                if a.sources else {}),
-                               **({"models": models} if models else {}), point_list=a.point_list, compat=a.compat)
+                               **({"models": models} if models else {}), point_list=a.point_list,
+                               compat="fixed" if a.tally_maps else a.compat, tally_maps=a.tally_maps)
     os.makedirs(a.out, exist_ok=True)
     tag = a.scenario + (f"_nk{a.wavenumbers}" if a.wavenumbers else "") + (f"_ns{a.sources}" if a.sources else "") + (
         f"_pc{a.point_charges}" if a.point_charges else "") + (f"_nm{a.models}" if a.models else "") + (
-        "_list" if a.point_list else "") + ("_tally" if a.tally else "_fixed" if a.compat == "fixed" else "")
+        "_list" if a.point_list else "") + (
+        "_tally" if a.tally else f"_maps{a.tally_maps}" if a.tally_maps else "_fixed" if a.compat == "fixed" else "")
     hip = os.path.join(a.out, f"{tag}.hip")
     with open(hip, "w") as f:
         f.write(src)

@@ -10,7 +10,16 @@ reported, with the walk-steps per second of both. Every step of a walk deposits 
 sample is clipped, so the tally's walk-steps per second bound its deposits (64-bit integer
 atomic adds) per second from above.
 
-Usage: python tools/tally_bench.py [--walks 16384] [--steps 200] [--repeats 3] [--json out.json]"""
+--channels (channel maps, DESIGN.md 7f "Channel maps"): dcr_dipole with --electrodes points, K = 8
+wavenumbers of wavenumber_quadrature(3, 30) at sigma_bar_for(k_max), grids of 32 x 16 and 256 x 128
+cells, R = 8. Four routes to the 2.5-D section alternate after a warm-up of each: the plain
+solve_wavenumbers launch (no map), one combined row w / 2 (one launch), the 8 unit rows (two
+launches of 4 maps) and the route without channel maps, 8 one-channel solve_greens_map calls on
+solvers with the explicit sigma = k^2 alpha. Medians of --repeats walk-kernel times, summed over a
+route's launches.
+
+Usage: python tools/tally_bench.py [--channels [--electrodes 16]] [--walks 16384] [--steps 200] [--repeats 3]
+       [--json out.json]"""
 import argparse
 import dataclasses
 import json
@@ -34,13 +43,105 @@ def cases(walks):
             ("poisson_square", sq, None, (-2.0, -2.0, 4.0, 4.0))]
 
 
+def _fitting(call):
+    """call(quantum) with the default quantum, or with the one its error message names."""
+    try:
+        call(None)
+        return None
+    except ValueError as e:
+        m = re.search(r"scale_log2 (-?\d+)", str(e))
+        if m is None:
+            raise
+        return 2.0 ** -int(m.group(1))
+
+
+def channel_mode(a):
+    from dcrmontecarlo_amd import scenarios as S
+    from dcrmontecarlo_amd import wavenumber as WN
+    from dcrmontecarlo_amd.greens_map import TallyGrid
+
+    sc = dataclasses.replace(S.dcr_dipole(a.electrodes, n_walks=a.walks), max_steps=a.steps)
+    k, w = WN.wavenumber_quadrature(3.0, 30.0, 8)
+    sb = WN.sigma_bar_for(sc, float(k.max()))
+    pts = np.ascontiguousarray(sc.points, np.float32)
+    kw = dict(maxSteps=a.steps, eps=sc.eps, seed=7)
+
+    def make(scn):
+        s = scn.solver(compat="fixed", device=0, sigma_bar=sb)
+        s.set_fixed_step_check(False)
+        s.set_option("jit_race", 0)
+        return s
+
+    multi = make(sc)
+    multi.set_wavenumbers(k)
+    singles = [make(dataclasses.replace(sc, sigma=sc.alpha * float(kj * kj))) for kj in k]
+    rows = []
+    for nx, ny in ((32, 16), (256, 128)):
+        grid = TallyGrid(-100.0, -100.0, 200.0 / nx, 200.0 / ny, nx, ny)
+        R = 8
+        q1 = _fitting(lambda q: multi.solve_greens_maps(pts, grid, w / 2.0, nWalks=a.walks, replicas=R, quantum=q, **kw))
+        q8 = _fitting(lambda q: multi.solve_greens_maps(pts, grid, np.eye(8), nWalks=a.walks, replicas=R, quantum=q, **kw))
+        qs = [_fitting(lambda q: s.solve_greens_map(pts, grid, nWalks=a.walks, replicas=R, quantum=q, **kw))
+              for s in singles]
+
+        def plain():
+            multi.solve_range(pts, a.walks, 0, a.walks, **kw)
+            return multi.last_timing["walk_kernel_ms"], multi.last_timing["total_steps"]
+
+        def combined():
+            multi.solve_greens_maps(pts, grid, w / 2.0, nWalks=a.walks, replicas=R, quantum=q1, **kw)
+            return multi.last_timing["walk_kernel_ms"]
+
+        def units():   # (solve_greens_maps keeps the last launch's timing: one launch per call here)
+            ms = 0.0
+            for t0 in (0, 4):
+                multi.solve_greens_maps(pts, grid, np.eye(8)[t0:t0 + 4], nWalks=a.walks, replicas=R, quantum=q8, **kw)
+                ms += multi.last_timing["walk_kernel_ms"]
+            return ms
+
+        def separate():
+            ms = 0.0
+            for s, q in zip(singles, qs):
+                s.solve_greens_map(pts, grid, nWalks=a.walks, replicas=R, quantum=q, **kw)
+                ms += s.last_timing["walk_kernel_ms"]
+            return ms
+
+        plain(), combined(), units(), separate()   # warm-up: every kernel compiled, buffers sized
+        t = {"plain": [], "combined": [], "units": [], "separate": []}
+        steps = 0
+        for _ in range(a.repeats):
+            ms, steps = plain()
+            t["plain"].append(ms)
+            t["combined"].append(combined())
+            t["units"].append(units())
+            t["separate"].append(separate())
+        med = {n: statistics.median(v) for n, v in t.items()}
+        rows.append({"problem": "dcr_dipole", "grid": f"{nx}x{ny}", "replicas": R, "points": len(pts), "walks": a.walks,
+                     "wavenumbers": 8, "sigma_bar": sb, "steps": int(steps), **{f"{n}_ms": v for n, v in med.items()},
+                     **{f"{n}_all_ms": v for n, v in t.items()}, "combined_over_separate": med["combined"] / med["separate"],
+                     "units_over_separate": med["units"] / med["separate"], "combined_over_plain": med["combined"] / med["plain"]})
+        print(f"dcr_dipole K=8 {nx:3d}x{ny:<3d} R={R}: plain {med['plain']:8.3f} ms, combined row {med['combined']:8.3f} ms, "
+              f"8 unit rows {med['units']:8.3f} ms, 8 one-channel solves {med['separate']:8.3f} ms; {steps:.3e} steps per "
+              f"walk set", flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--walks", type=int, default=16384)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--channels", action="store_true", help="the channel-map routes to a 2.5-D section")
+    ap.add_argument("--electrodes", type=int, default=16, help="--channels: query points")
     a = ap.parse_args()
+    if a.channels:
+        rows = channel_mode(a)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(rows, f, indent=1)
+                f.write("\n")
+        return
     from dcrmontecarlo_amd.greens_map import TallyGrid
 
     rows = []
